@@ -22,6 +22,19 @@ Other BASELINE.json configs (same step, same JSON line):
   semantics, as the reference recipe) — it needs ≈51 GB of the 288 GB of HBM, measured
   (profiles/cfg5_slice_r2.json). ``--micro_batch V`` switches to gradient-cache chunks
   of V views (per-chunk BN statistics, see engine/pretrain.py) for larger batches.
+
+A plain run does only what the headline figure needs: set-up, W warm-up steps, the K timed
+steps, the JSON line (for N>1 with ``--syncbn_comm auto`` set-up includes the transport choice:
+3 timed steps per candidate, twice, state restored). ``--full`` adds the diagnostics that take steps of their own: the
+idle-queue host issue time (3 extra steps between warm-up and the timed region, stderr) and,
+for N>1, the local-BN baseline of the SyncBN transport timing (``syncbn_us_per_bn``).
+
+``--dump-outputs DIR`` writes, after the timed steps, what the last timed step returned and
+left behind as ``DIR/<name>.npy`` (float32): every tensor of the step's statistics dict
+(``loss_local``, feature-norm statistics) and a fixed seeded sample of the updated master
+parameters (``params``) and of the step's gradient (``grads``); ``sample_index.npy``
+(float64) holds the sampled positions. Data, weights, batch order and augmentation draws are
+seeded, so the inputs are the same from run to run. For N>1 rank 0 writes its own view.
 """
 from __future__ import annotations
 
@@ -58,6 +71,29 @@ def _self_launch(n: int) -> int:
     return subprocess.call(cmd, env=env)
 
 
+DUMP_SAMPLE = 1 << 21      # elements kept of each flat buffer (8 MB as float32)
+
+
+def _dump_outputs(path: str, eng, stats: dict) -> None:
+    """``--dump-outputs``: the last timed step's results as float32 ``.npy`` files (< 64 MB)."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    out = {k: v.detach().float().cpu().numpy() for k, v in stats.items() if isinstance(v, torch.Tensor)}
+    total = eng.flat.flat.numel()
+    if total > DUMP_SAMPLE:
+        g = torch.Generator().manual_seed(0)
+        sel = torch.randperm(total, generator=g)[:DUMP_SAMPLE].sort().values
+    else:
+        sel = torch.arange(total)
+    dsel = sel.to(eng.flat.flat.device)
+    out["params"] = eng.flat.flat.detach()[dsel].float().cpu().numpy()
+    out["grads"] = eng.flat.grad.detach()[dsel].float().cpu().numpy()
+    for k, v in out.items():
+        np.save(os.path.join(path, f"{k}.npy"), np.ascontiguousarray(v, dtype=np.float32))
+    np.save(os.path.join(path, "sample_index.npy"), sel.numpy().astype(np.float64))
+
+
 def main():
     pre = argparse.ArgumentParser(add_help=False)
     pre.add_argument("--gpus", type=int, default=1)
@@ -82,6 +118,11 @@ def main():
     ap.add_argument("--no_syncbn", action="store_true")
     ap.add_argument("--graph", type=int, default=0,
                     help="capture the step in a hipGraph (single GPU; measured slower than eager + wgrad side stream)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the diagnostics that take steps of their own: idle-queue host issue time "
+                         "(stderr) and, for N>1, the local-BN baseline of the SyncBN transport timing")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the last step's results as DIR/<name>.npy (float32)")
     a, extra = ap.parse_known_args()
 
     import torch
@@ -142,8 +183,8 @@ def main():
 
     # N > 1: the SyncBN transport candidates of --syncbn_comm (default rccl: RCCL only; auto: the
     # fused xGMI exchange too) are timed on real steps (state restored afterwards), the ranks
-    # agree on the fastest; reported in the JSON line with a local-BN baseline
-    tune = eng.autotune_syncbn(next_idx(0), steps=3, baseline=True) if n > 1 and not a.no_syncbn else None
+    # agree on the fastest; reported in the JSON line, under --full with a local-BN baseline
+    tune = eng.autotune_syncbn(next_idx(0), steps=3, baseline=a.full) if n > 1 and not a.no_syncbn else None
     graphed = False
     if a.graph:
         # capture the whole step in one hipGraph (its 2 capture warm-up steps are real steps)
@@ -159,15 +200,16 @@ def main():
             # dict is the captured graph's persistent output, overwritten by every replay
             first_loss = st0["loss_local"].detach().clone()
     sync()
-    # host cost of issuing one step into an idle queue (diagnostic, stderr)
+    # --full: host cost of issuing one step into an idle queue (diagnostic, stderr)
     th = []
-    for i in range(3):
+    for i in range(3 if a.full else 0):
         sync()
         t = time.perf_counter()
         eng.train_step(next_idx(i), 1, i % iters, iters)
         th.append(time.perf_counter() - t)
         sync()
-    print(f"host issue time (idle queue) {min(th) * 1e3:.3f} ms/step", file=sys.stderr)
+    if th:
+        print(f"host issue time (idle queue) {min(th) * 1e3:.3f} ms/step", file=sys.stderr)
     t0 = time.perf_counter()
     for i in range(a.steps):
         st = eng.train_step(next_idx(i), 1, i % iters, iters)
@@ -179,6 +221,8 @@ def main():
     if n > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt = float(t.item())
+    if a.dump_outputs and comm.rank() == 0:
+        _dump_outputs(a.dump_outputs, eng, st)
     loss = float(st["loss_local"].item())
     loss0 = float(first_loss.item()) if first_loss is not None else None
     ms = dt / a.steps * 1e3
@@ -210,7 +254,7 @@ def main():
                        # lr 0.5 / no warm-up also reaches in fp32 torch on synthetic data in the
                        # first ~20-60 steps: profiles/convergence_r1.txt)
                        "first_loss_local": round(loss0, 4) if loss0 is not None else None,
-                       "last_loss_local": round(loss, 4), "loss_steps": a.warmup + 3 + a.steps},
+                       "last_loss_local": round(loss, 4), "loss_steps": a.warmup + len(th) + a.steps},
         }), flush=True)
     if dist.is_initialized():
         dist.destroy_process_group()

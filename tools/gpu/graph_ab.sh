@@ -14,7 +14,7 @@ for b in 256 128; do
     [ $mode = g1side ] && side=1
     [ $mode = g1side ] && [ $b = 128 ] && continue
     tag=b${b}_${mode}
-    SDX_GRAPH_SIDE=$side timeout -k 10 200 python bench.py --per_gpu_batch $b --graph $g --steps 40 --warmup 10 > $O/$tag.txt 2>&1 || { tail -5 $O/$tag.txt; exit 1; }
+    SDX_GRAPH_SIDE=$side timeout -k 10 200 python bench.py --full --per_gpu_batch $b --graph $g --steps 40 --warmup 10 > $O/$tag.txt 2>&1 || { tail -5 $O/$tag.txt; exit 1; }
     echo "$tag $(grep -o '"ms_per_step": [0-9.]*' $O/$tag.txt) $(grep -o '"hip_graph": [a-z]*' $O/$tag.txt) $(grep 'idle queue' $O/$tag.txt)" | tee -a $O/summary.txt
   done
 done

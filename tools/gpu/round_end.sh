@@ -11,8 +11,8 @@ mkdir -p $O
 timeout -k 10 1000 python -u -m pytest tests -m gpu -v --timeout 300 --timeout-method thread > $O/gpu_tests.txt 2>&1; rc=$?; [ $rc -le 1 ] || exit $rc
 grep -E "passed|failed" $O/gpu_tests.txt | tail -n 2
 timeout -k 10 200 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.txt 2>&1 || exit 1
-timeout -k 10 200 python -u bench.py > $O/bench1.txt 2>&1 || exit 1
-timeout -k 10 200 python -u bench.py --steps 40 --warmup 10 > $O/bench2.txt 2>&1 || exit 1
+timeout -k 10 200 python -u bench.py --full > $O/bench1.txt 2>&1 || exit 1
+timeout -k 10 200 python -u bench.py --full --steps 40 --warmup 10 > $O/bench2.txt 2>&1 || exit 1
 # hipGraph replay of the same step (captured as one chain) and its ratio to eager
 timeout -k 10 200 python -u bench.py --graph 1 --steps 40 --warmup 10 > $O/bench_graph.txt 2>&1 || exit 1
 python - $O/bench2.txt $O/bench_graph.txt <<'PY' | tee $O/graph_ratio.txt

@@ -17,7 +17,7 @@ mkdir -p $O
 run() {  # $1 = tag, rest = extra bench args
   tag=$1_np$NP$SFX; shift
   timeout -k 10 $TLIM python -m torch.distributed.run --nnodes=1 --nproc-per-node $NP --master-addr 127.0.0.1 \
-    --master-port $PORT bench.py --gpus $NP --steps 10 --warmup 3 $BENCH_ARGS "$@" > $O/$tag.log 2>&1
+    --master-port $PORT bench.py --gpus $NP --full --steps 10 --warmup 3 $BENCH_ARGS "$@" > $O/$tag.log 2>&1
 }
 run nccl; rc=$?
 echo "nccl rc=$rc"; grep '"metric"' $O/nccl_np$NP$SFX.log || tail -15 $O/nccl_np$NP$SFX.log
