@@ -25,12 +25,19 @@ void sgd_step(torch::Tensor p, torch::Tensor g, torch::Tensor buf, torch::Tensor
 }
 
 void lars_step(torch::Tensor p, torch::Tensor g, torch::Tensor buf, torch::Tensor seg_off, torch::Tensor adapt,
-               torch::Tensor lr, double momentum, double wd, double gscale, double eta, torch::Tensor norms) {
+               torch::Tensor lr, double momentum, double wd, double gscale, double eta, torch::Tensor norms,
+               torch::Tensor partials) {
   const int64_t n = p.numel();
   check_flat(p, n, "p");
   check_flat(g, n, "g");
   check_flat(buf, n, "buf");
+  // one 4096-element block never straddles two segments, and owns one scratch slot
+  TORCH_CHECK(n % 4096 == 0, "flat size must be a multiple of 4096");
   const int64_t nseg = seg_off.numel();
+  TORCH_CHECK(nseg >= 1, "empty segment table");
+  TORCH_CHECK(partials.is_cuda() && partials.scalar_type() == at::kFloat && partials.is_contiguous() &&
+                  partials.numel() == 2 * (n / 4096),
+              "partials [2*n/4096] float32");
   TORCH_CHECK(seg_off.is_cuda() && seg_off.scalar_type() == at::kLong && seg_off.is_contiguous(), "seg_off int64");
   TORCH_CHECK(adapt.is_cuda() && adapt.scalar_type() == at::kInt && adapt.numel() == nseg, "adapt int32[nseg]");
   TORCH_CHECK(norms.is_cuda() && norms.scalar_type() == at::kFloat && norms.numel() == 2 * nseg, "norms [2*nseg]");
@@ -38,7 +45,7 @@ void lars_step(torch::Tensor p, torch::Tensor g, torch::Tensor buf, torch::Tenso
   c10::DeviceGuard dg(p.device());
   check_hip(launch_lars(p.data_ptr<float>(), g.data_ptr<float>(), buf.data_ptr<float>(), seg_off.data_ptr<int64_t>(),
                         adapt.data_ptr<int>(), (int)nseg, n, lr.data_ptr<float>(), (float)momentum, (float)wd,
-                        (float)gscale, (float)eta, norms.data_ptr<float>(), cur_stream()),
+                        (float)gscale, (float)eta, norms.data_ptr<float>(), partials.data_ptr<float>(), cur_stream()),
             "lars_step");
 }
 
@@ -57,7 +64,8 @@ void register_optim(pybind11::module& m) {
   m.def("sgd_step", &sgd_step, "fused flat-buffer SGD (momentum, wd, grad scale, device lr)", pybind11::arg("p"),
         pybind11::arg("g"), pybind11::arg("buf"), pybind11::arg("lr"), pybind11::arg("momentum"), pybind11::arg("wd"),
         pybind11::arg("gscale"), pybind11::arg("nesterov"), pybind11::arg("max_blocks") = 0);
-  m.def("lars_step", &lars_step, "fused flat-buffer LARS");
+  m.def("lars_step", &lars_step, "fused flat-buffer LARS; norms [2*nseg] receives each segment's sum p^2, sum d^2 (deterministic: "
+        "per-block partials in the scratch `partials` [2*n/4096], summed in index order)");
 }
 
 }  // namespace sdx_bind

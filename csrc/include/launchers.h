@@ -283,7 +283,7 @@ hipError_t launch_sgd(float* p, const float* g, float* buf, long n, const float*
                       float gscale, int nesterov, hipStream_t s, int max_blocks = 0);
 hipError_t launch_lars(float* p, const float* g, float* buf, const long* seg_off, const int* adapt, int nseg, long n,
                        const float* lr, float momentum, float wd, float gscale, float eta, float* norms,
-                       hipStream_t s);
+                       float* part, hipStream_t s);
 
 // ---- pooling (pool.hip) ---------------------------------------------------------
 hipError_t launch_maxpool_fwd(const void* x, void* y, int N, int H, int W, int C, int P, int Q, int k, int stride,

@@ -49,11 +49,25 @@ __device__ __forceinline__ int find_seg(const long* __restrict__ off, int nseg, 
   return lo;
 }
 
-// per-segment Σp² and Σ(s·g + wd·p)² (wd only on adapted segments) -> out[2*nseg] (zeroed)
+// block-wide sum in a fixed order: xor butterfly inside each wave, then the four wave sums in
+// wave order. Every thread returns the same value. `red` holds 4 floats.
+__device__ __forceinline__ float block_sum_ordered(float v, float* red) {
+  v = wave_sum(v);
+  __syncthreads();   // `red` may still be read from an earlier call
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// per-block partial sums: part[2*blk] = Σp², part[2*blk+1] = Σ(s·g + wd·p)² (wd only on adapted
+// segments) over the block's 4096 elements. No atomics: every block owns its slot, and the sum
+// inside a block has a fixed order (16 terms per thread, butterfly, 4 waves), so the norms are
+// bit-reproducible from run to run and from rank to rank.
 __global__ __launch_bounds__(256) void seg_norms_kernel(const float* __restrict__ p, const float* __restrict__ g,
                                                         const long* __restrict__ off, const int* __restrict__ adapt,
                                                         int nseg, long n, float wd, float gscale,
-                                                        float* __restrict__ out) {
+                                                        float* __restrict__ part) {
+  __shared__ float red[4];
   // each block handles a contiguous chunk of 4096 elements; chunks never straddle segments
   // because every segment is padded to a multiple of 4096 by the flat-buffer allocator.
   const long base = (long)blockIdx.x * 4096;
@@ -67,29 +81,46 @@ __global__ __launch_bounds__(256) void seg_norms_kernel(const float* __restrict_
     sp += pv * pv;
     sd += d * d;
   }
-  sp = wave_sum(sp);
-  sd = wave_sum(sd);
-  if ((threadIdx.x & 63) == 0) {
-    atomicAdd(out + 2 * seg, sp);
-    atomicAdd(out + 2 * seg + 1, sd);
-  }
+  sp = block_sum_ordered(sp, red);
+  sd = block_sum_ordered(sd, red);
+  if (threadIdx.x == 0) *reinterpret_cast<float2*>(part + 2 * (long)blockIdx.x) = make_float2(sp, sd);
 }
 
 // LARS: d = s·g + wd·p (adapted) | s·g; trust = eta·||p||/||d|| (adapted, both > 0) | 1;
 // buf = m·buf + lr·trust·d; p -= buf
+// Every block sums the partials of its own segment in index order (thread t takes blocks
+// t, t+256, ... of the segment, then the fixed-order block sum): all blocks of a segment get
+// the same bits, and the segment's first block stores them to norms[2*seg], norms[2*seg+1].
 __global__ __launch_bounds__(256) void lars_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                    float* __restrict__ buf, const long* __restrict__ off,
-                                                   const int* __restrict__ adapt, const float* __restrict__ norms,
-                                                   int nseg, long n, const float* __restrict__ lr_ptr, float momentum,
-                                                   float wd, float gscale, float eta) {
+                                                   const int* __restrict__ adapt, const float* __restrict__ part,
+                                                   float* __restrict__ norms, int nseg, long n,
+                                                   const float* __restrict__ lr_ptr, float momentum, float wd,
+                                                   float gscale, float eta) {
+  __shared__ float red[4];
   const float lr = lr_ptr[0];
   const long base = (long)blockIdx.x * 4096;
   if (base >= n) return;
   const int seg = find_seg(off, nseg, base);
+  // clamped to the scratch's n/4096 slots whatever the table holds
+  const long blk0 = max(off[seg], 0L) / 4096;
+  const long blk1 = min(seg + 1 < nseg ? off[seg + 1] : n, n) / 4096;
+  float sp = 0.f, sd = 0.f;
+  for (long b = blk0 + threadIdx.x; b < blk1; b += 256) {
+    const float2 v = *reinterpret_cast<const float2*>(part + 2 * b);
+    sp += v.x;
+    sd += v.y;
+  }
+  sp = block_sum_ordered(sp, red);
+  sd = block_sum_ordered(sd, red);
+  if (blockIdx.x == blk0 && threadIdx.x == 0) {
+    norms[2 * seg] = sp;
+    norms[2 * seg + 1] = sd;
+  }
   const bool ad = adapt[seg] != 0;
   float trust = 1.f;
   if (ad) {
-    const float pn = sqrtf(norms[2 * seg]), dn = sqrtf(norms[2 * seg + 1]);
+    const float pn = sqrtf(sp), dn = sqrtf(sd);
     if (pn > 0.f && dn > 0.f) trust = eta * pn / dn;
   }
   const float w = ad ? wd : 0.f;
@@ -120,16 +151,18 @@ hipError_t launch_sgd(float* p, const float* g, float* buf, long n, const float*
   return hipSuccess;
 }
 
+// n and every seg_off entry are multiples of 4096 (checked by the binding); part holds
+// 2 * n/4096 floats, norms 2 * nseg. Both are fully overwritten, nothing needs zeroing.
 hipError_t launch_lars(float* p, const float* g, float* buf, const long* seg_off, const int* adapt, int nseg, long n,
-                       const float* lr, float momentum, float wd, float gscale, float eta, float* norms,
+                       const float* lr, float momentum, float wd, float gscale, float eta, float* norms, float* part,
                        hipStream_t s) {
-  hipError_t e = hipMemsetAsync(norms, 0, sizeof(float) * 2 * nseg, s);
-  if (e != hipSuccess) return e;
-  const long blocks = (n + 4095) / 4096;
+  if (n % 4096 != 0 || nseg < 1) return hipErrorInvalidValue;
+  const long blocks = n / 4096;
+  if (blocks < 1) return hipSuccess;
   hipLaunchKernelGGL(seg_norms_kernel, dim3(blocks), dim3(256), 0, s, p, g, seg_off, adapt, nseg, n, wd, gscale,
-                     norms);
+                     part);
   SDX_LAUNCH_CHECK();
-  hipLaunchKernelGGL(lars_kernel, dim3(blocks), dim3(256), 0, s, p, g, buf, seg_off, adapt, norms, nseg, n, lr,
+  hipLaunchKernelGGL(lars_kernel, dim3(blocks), dim3(256), 0, s, p, g, buf, seg_off, adapt, part, norms, nseg, n, lr,
                      momentum, wd, gscale, eta);
   SDX_LAUNCH_CHECK();
   return hipSuccess;

@@ -196,6 +196,8 @@ class FusedLARS(_FlatOptimizer):
         self.seg_off = torch.tensor(offs, dtype=torch.int64, device=dev)
         self.adapt = torch.tensor(adapt, dtype=torch.int32, device=dev)
         self.norms = torch.zeros(2 * len(offs), dtype=torch.float32, device=dev)
+        # per-4096-block partial sums of the norms pass (summed in index order: deterministic)
+        self.partials = torch.zeros(2 * (flat.total // SEG_ALIGN), dtype=torch.float32, device=dev)
         self.native = backend != "torch" and flat.flat.is_cuda and _ext.available()
 
     @torch.no_grad()
@@ -205,7 +207,7 @@ class FusedLARS(_FlatOptimizer):
         f = self.flat
         if self.native:
             _ext.require().lars_step(f.flat, f.grad, self.buf, self.seg_off, self.adapt, self.lr_t, self.momentum,
-                                     self.weight_decay, self.grad_scale, self.eta, self.norms)
+                                     self.weight_decay, self.grad_scale, self.eta, self.norms, self.partials)
         else:
             for i, p in enumerate(f.params):
                 pv = f._view(f.flat, i)

@@ -1,5 +1,9 @@
 """GPU: augmentation kernel vs the torch reference with identical draws; fused SGD/LARS
-kernels vs the torch fallback; native end-to-end step (engine) runs and is finite."""
+kernels vs the torch fallback; native end-to-end step (engine) runs and is finite.
+
+The independent checks of these two kernels live elsewhere: tests/test_gpu_augment.py (each
+augmentation stage against the fp64 oracle tests/aug_oracle.py) and tests/test_gpu_optim.py
+(sgd_step / lars_step on hand-made flat buffers against fp64 oracles)."""
 import pytest
 import torch
 

@@ -42,10 +42,34 @@ def test_flat_views_keep_channels_last():
 
 
 def test_lars_runs_and_excludes_bn():
+    """First step of the torch path against the fp64 definition: 1-D parameters (BN, biases)
+    move by exactly lr*s*g (no weight decay, no trust scaling); >=2-D parameters move by
+    lr*eta*||p||/||d||*d with d = s*g + wd*p."""
     m = _tiny()
     flat = FlatParams(m)
-    o = FusedLARS(flat, lr=1.0, momentum=0.9, weight_decay=1e-4, backend="torch")
+    lr, wd, eta, s = 1.0, 1e-2, 1e-3, 0.5
+    o = FusedLARS(flat, lr=lr, momentum=0.9, weight_decay=wd, eta=eta, backend="torch")
+    o.grad_scale = s
+    m(torch.randn(4, 3, 8, 8)).tanh().sum().backward()
     before = [p.detach().clone() for p in m.parameters()]
-    m(torch.randn(4, 3, 8, 8)).sum().backward()
+    grads = [p.grad.detach().clone() for p in m.parameters()]
     o.step()
     assert all(not torch.equal(p, q) for p, q in zip(m.parameters(), before))
+    u = 2.0 ** -24
+    seen = set()
+    for p, p0, g in zip(m.parameters(), before, grads):
+        p0d, gd = p0.double(), g.double()
+        seen.add(min(p.dim(), 2))
+        if p.dim() == 1:
+            want = p0d - lr * s * gd
+            # with weight decay or a trust ratio the step would be off by >= wd*|p| or ~1000x
+            tol = 4 * u * (p0d.abs() + (lr * s * gd).abs())
+        else:
+            d = s * gd + wd * p0d
+            trust = eta * p0d.norm() / d.norm()
+            assert 0 < float(trust) < 1
+            want = p0d - lr * trust * d
+            # fp32 norms over <= 288 terms (gamma_n each, halved by the roots), a few products
+            tol = 4 * u * p0d.abs() + (p.numel() + 8) * u * (lr * trust * ((s * gd).abs() + (wd * p0d).abs()))
+        assert bool(((p.detach().double() - want).abs() <= tol).all()), p.shape
+    assert seen == {1, 2}
