@@ -12,6 +12,7 @@ void register_xgmi(pybind11::module& m);
 void register_comm(pybind11::module& m);
 void register_head(pybind11::module& m);
 void register_probe(pybind11::module& m);
+void register_knn(pybind11::module& m);
 
 void register_ops(pybind11::module& m) {
   register_supcon(m);
@@ -24,5 +25,6 @@ void register_ops(pybind11::module& m) {
   register_comm(m);
   register_head(m);
   register_probe(m);
+  register_knn(m);
 }
 }  // namespace sdx_bind

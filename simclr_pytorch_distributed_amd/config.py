@@ -9,7 +9,8 @@ Additions (new flags only; no reference flag changes meaning):
 ``--local-rank`` (dashed alias), env rank discovery (Q13),
 ``--precision``, ``--backend``, ``--synthetic``, ``--stem``, ``--optimizer {sgd,lars}``,
 ``--grad_semantics {ref,exact}`` (Q2), ``--dist_backend``, ``--seed``, ``--head``,
-``--feat_dim`` (Q11), ``--resume``, ``--cuda_graph``, ``--work_dir``.
+``--feat_dim`` (Q11), ``--resume``, ``--cuda_graph``, ``--work_dir``,
+``--knn_freq`` / ``--knn`` with ``--knn_k`` / ``--knn_t`` (weighted k-NN monitor, engine/knn.py).
 Fixes: ``--num_workers`` is honoured (Q6): it sizes the image-decode thread pool of
 ``dataset=path`` and the CPU augmentation threads of ``--gpu_aug 0`` (the default pipeline
 is the GPU kernel, which needs no workers); ``dataset=path`` parses ``--mean/--std``
@@ -88,6 +89,11 @@ def _add_common_new_flags(p: argparse.ArgumentParser):
                    help="per-phase HIP-event timings in the log + ROCTX ranges for rocprofv3 --marker-trace")
 
 
+def _add_knn_flags(g):
+    g.add_argument("--knn_k", type=int, default=200, help="neighbours of the weighted k-NN evaluation")
+    g.add_argument("--knn_t", type=float, default=0.1, help="temperature of the k-NN vote exp(sim/T)")
+
+
 def pretrain_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser("argument for training")
     # main_supcon.py:26-34
@@ -139,6 +145,10 @@ def pretrain_parser() -> argparse.ArgumentParser:
     g.add_argument("--micro_batch", type=int, default=0,
                    help="gradient-cache micro-batching: encoder forward/backward in chunks of this many "
                         "VIEWS per rank (0 = whole local batch); the contrastive loss still sees the full batch")
+    g.add_argument("--knn_freq", type=int, default=0,
+                   help="weighted k-NN accuracy of the encoder on the validation split every N epochs and "
+                        "after the last epoch (0 = off)")
+    _add_knn_flags(g)
     _add_common_new_flags(p)
     return p
 
@@ -178,6 +188,11 @@ def parse_pretrain(argv: Optional[Sequence[str]] = None, make_dirs: bool = True,
     opt = pretrain_parser().parse_args(argv)
     if opt.dataset == "path":
         assert opt.data_folder is not None and opt.mean is not None and opt.std is not None
+    if opt.knn_freq < 0 or opt.knn_k < 1 or not opt.knn_t > 0:
+        raise ValueError("--knn_freq >= 0, --knn_k >= 1 and --knn_t > 0 are required")
+    if opt.knn_freq > 0 and opt.dataset == "path":
+        raise ValueError("--knn_freq needs a dataset with a validation split (cifar10, cifar100 or --synthetic); "
+                         "--dataset path has none")
     rank, local_rank, world = env_rank_info(opt.local_rank)
     opt.rank, opt.local_rank = rank, local_rank
     if opt.ngpu is None:
@@ -244,6 +259,9 @@ def linear_parser() -> argparse.ArgumentParser:
     g.add_argument("--data_folder", type=str, default="./datasets/")
     g.add_argument("--val_batch_size", type=int, default=256)
     g.add_argument("--local_rank", "--local-rank", dest="local_rank", type=int, default=0)
+    g.add_argument("--knn", action="store_true",
+                   help="report the loaded checkpoint's weighted k-NN accuracy before classifier training")
+    _add_knn_flags(g)
     _add_common_new_flags(p)
     return p
 
@@ -251,6 +269,8 @@ def linear_parser() -> argparse.ArgumentParser:
 def parse_linear(argv: Optional[Sequence[str]] = None, make_dirs: bool = True,
                  now: Optional[datetime.datetime] = None):
     opt = linear_parser().parse_args(argv)
+    if opt.knn_k < 1 or not opt.knn_t > 0:
+        raise ValueError("--knn_k >= 1 and --knn_t > 0 are required")
     rank, local_rank, world = env_rank_info(opt.local_rank)
     opt.rank, opt.local_rank, opt.world_size = rank, local_rank, world
     _finish_common(opt, True)

@@ -184,9 +184,25 @@ class LinearEngine:
         logging.info(" * Acc@1 {top1.avg:.3f}, Acc@5 {top5.avg:.3f}".format(top1=top1, top5=top5))
         return losses.avg, top1.avg, top5.avg
 
+    def knn_eval(self):
+        """--knn: weighted k-NN accuracy of the loaded encoder (tags knn/val_acc1, knn/val_acc5 at step 0)."""
+        from .knn import KnnEvaluator
+        opt = self.opt
+        t0 = time.time()
+        ev = KnnEvaluator(self.model, self.backend, opt.precision, self.tr_x, self.tr_y, self.va_x, self.va_y,
+                          opt.mean_t, opt.std_t, 32, opt.n_cls, opt.knn_k, opt.knn_t,
+                          runner=self.runner if self.backend != "native" else None)
+        acc1, acc5 = ev.evaluate()
+        logging.info("kNN: epoch {} Acc@1 {:.2f} Acc@5 {:.2f} ({:.2f}s)".format(0, acc1, acc5, time.time() - t0))
+        self.logger.log_value("knn/val_acc1", acc1, 0)
+        self.logger.log_value("knn/val_acc5", acc5, 0)
+        return acc1, acc5
+
     def run(self):
         opt = self.opt
         best_acc, best_acc5 = 0.0, 0.0
+        if getattr(opt, "knn", False):
+            self.knn_eval()
         for epoch in range(1, opt.epochs + 1):
             adjust_learning_rate(opt, self.optimizer, epoch)
             t1 = time.time()

@@ -183,8 +183,38 @@ class PretrainEngine:
         self._graph = None
         self._graph_stats = None
         self.prof = PhaseTimer(getattr(opt, "profile", False), dev)
+        self.knn = None
+        if getattr(opt, "knn_freq", 0) > 0:
+            self.knn = self._build_knn(ds)
         if getattr(opt, "resume", ""):
             self._resume(opt.resume)
+
+    def _build_knn(self, train_ds):
+        """The weighted k-NN monitor (--knn_freq): bank = the training images already resident
+        on the device, queries = the validation split, loaded here once."""
+        from .knn import KnnEvaluator
+        opt = self.opt
+        if train_ds.ragged:
+            raise ValueError("--knn_freq needs a fixed-size dataset with a validation split")
+        va = build_dataset(opt.dataset, opt.data_folder, False, opt.synthetic, opt.synthetic_size, opt.size, opt.seed,
+                           workers=opt.num_workers)
+        n_cls = opt.n_cls or int(max(int(train_ds.labels.max()), int(va.labels.max()))) + 1
+        return KnnEvaluator(self.model, self.backend, opt.precision, self.data, self.labels,
+                            torch.from_numpy(va.images).to(self.device), torch.from_numpy(va.labels).to(self.device),
+                            opt.mean_t, opt.std_t, opt.size, n_cls, opt.knn_k, opt.knn_t,
+                            runner=self.runner if self.backend != "native" else None)
+
+    def knn_eval(self, epoch: int):
+        """Run the k-NN monitor, log it and (rank 0) write knn/val_acc1, knn/val_acc5."""
+        t0 = time.time()
+        acc1, acc5 = self.knn.evaluate()
+        if self.device.type == "cuda":
+            torch.cuda.synchronize()
+        logging.info("kNN: epoch {} Acc@1 {:.2f} Acc@5 {:.2f} ({:.2f}s)".format(epoch, acc1, acc5, time.time() - t0))
+        if self.rank == 0:
+            self.logger.log_value("knn/val_acc1", acc1, epoch)
+            self.logger.log_value("knn/val_acc5", acc5, epoch)
+        return acc1, acc5
 
     # ------------------------------------------------------------------------------
     # SyncBN statistics transport actually in use (bench.py reports it): none (W=1),
@@ -731,6 +761,8 @@ class PretrainEngine:
             if self.rank == 0:
                 self.logger.log_value("loss", loss, epoch)
                 self.logger.log_value("learning_rate", self.optimizer.param_groups[0]["lr"], epoch)
+            if self.knn is not None and (epoch % opt.knn_freq == 0 or epoch == opt.epochs):
+                self.knn_eval(epoch)
             if epoch % opt.save_freq == 0 and self.rank == 0:
                 f = os.path.join(opt.save_folder, f"ckpt_epoch_{epoch}.pth")
                 ckpt_mod.save_model(self.model, self.optimizer, opt, epoch, f, self._extra_state(epoch))
