@@ -250,10 +250,7 @@ int64_t add(std::shared_ptr<SmallComm> c) {
 
 // SDX_SYNCBN_FUSED=0: the xGMI kinds fall back to reduce -> one-shot all-reduce -> finalize
 bool fused_disabled() {
-  static const bool off = [] {
-    const char* e = getenv("SDX_SYNCBN_FUSED");
-    return e != nullptr && atoi(e) == 0;
-  }();
+  static const bool off = !sdx_plan::env_flag("SDX_SYNCBN_FUSED", true);
   return off;
 }
 

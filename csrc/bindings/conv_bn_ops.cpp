@@ -9,13 +9,15 @@
 #include <c10/hip/HIPStream.h>
 
 #include <atomic>
-#include <cmath>
 #include <map>
 #include <mutex>
+#include <utility>
 
 namespace sdx_bind {
 
 using OptT = c10::optional<torch::Tensor>;
+using sdx_plan::knobs;
+using sdx_plan::knobs_mut;
 
 void check_bf16_nhwc(const torch::Tensor& t, const char* name) {
   TORCH_CHECK(t.is_cuda(), name, " must be a GPU tensor");
@@ -43,109 +45,12 @@ void in_bn_ptrs(const OptT& sc, const OptT& sh, int64_t C, const float** ps, con
   TORCH_CHECK((*ps == nullptr) == (*pt == nullptr), "in_scale and in_shift must be given together");
 }
 
-// Pick the tile config (0 128x128, 1 256x64, 2 64x256, 3 64x64) minimising
-//   padded work x per-config efficiency penalty x grid fill,
-// where fill = (launch rounds x resident slots) / tiles charges a grid that leaves CUs idle
-// in its last round (e.g. M=8192 x N=512: 256 tiles of 128x128 fill only half of the 512
-// two-per-CU slots). The small 64x64 tile is only penalised when the GEMM is
-// compute-bound (long K); short-K (memory-bound) GEMMs favour its higher occupancy.
-// Calibrated with tools/conv_bench.py --cfg 0..3 on the ResNet-50 shapes.
-// SDX_CONV_CFG=c pins the fwd/dgrad tile config (tests): the BN-statistics epilogue's per-tile
-// fp32 partial sums then cover the same rows whatever the per-rank batch, so a W-rank step
-// reproduces the single-rank statistics bit for bit (tests/test_gpu_dist.py)
-int pinned_cfg() {
-  static const int pinned = [] {
-    const char* e = getenv("SDX_CONV_CFG");
-    const int v = e != nullptr ? atoi(e) : -1;
-    return v >= 0 && v <= 8 ? v : -1;
-  }();
-  return pinned;
-}
-
-// fwd / dgrad tile config of a conv: the tap-reuse 3x3 loop where it applies (pad-1 stride-1
-// 3x3; not with a pinned config, the in-kernel statistics reduction or the BN+ReLU operand
-// prologue), else auto_cfg. SDX_TAP3=0 disables it. Per shape (tools/tap3_sweep.py,
-// profiles/tap3_r5.txt) it beats the best implicit-GEMM tile at every CIFAR ResNet-50 3x3:
-// fwd / dgrad l1 52 / 51 vs 67 / 68 us, l2 45 / 42 vs 47 / 45, l3 34 / 34 vs 38 / 37,
-// l4 38 / 38 vs 58 / 56
-std::atomic<int>& tap3_flag() {
-  static std::atomic<int> on{[] {
-    const char* e = getenv("SDX_TAP3");
-    return e == nullptr ? 1 : atoi(e);
-  }()};
-  return on;
-}
-
+// Every dispatch decision (tile config, main loop, splits, slab rows) is a plan of
+// conv_plan.h under the process's knobs; the setters below write those knobs.
 // runtime switch of the tap-reuse loop (tests / in-process A/B); returns the previous value
-int64_t tap3_set(int64_t on) { return tap3_flag().exchange((int)on); }
+int64_t tap3_set(int64_t on) { return std::exchange(knobs_mut().tap3, (int)on); }
 
-//
-// Then per-pass corrections to auto_cfg from the round-5 re-calibration (every fwd / dgrad
-// of the CIFAR ResNet-50 at 512 views under every tile config, the dgrads with their
-// BN-statistics epilogue: tools/cfg_sweep.py, profiles/cfg_sweep_r5.txt; 5.32 -> 5.24 ms
-// summed stand-alone). Three corrections won stand-alone; in the step (bench A/B, same box,
-// SDX_CFG_RULES bit mask) only bit 4 does, so it alone is on by default:
-//  1 the 128x256 DEPTH-6 tile only when it fills the chip (>= 256 tiles): l4 1x1 / strided
-//    3x3 fwd at M = 8192 on the 8-wave 128x128 (52.8 vs 58.1 us) — neutral in the step;
-//  2 expanding stride-1 dgrads (dx has >= 256 and >= twice the reduction's channels) on the
-//    64x256 tile (l1 137.8 vs 146.3 us) — +0.05 ms in the step (12.21 vs 12.155 ms): more
-//    blocks per CU under the heavy epilogue is exactly what the side-stream wgrads lose;
-//  4 strided dgrads with 256-multiple outputs on DEPTH 6 (l3.0 3x3 84.4 vs 90.4 us, l3.0
-//    shortcut 127.3 vs 135.9) — -0.03 ms in the step (12.12 vs 12.155)
-int conv_cfg(const ConvGeom& g, int cdim, int ncol, int64_t M, int64_t Kdim, bool plain, bool dgrad) {
-  if (tap3_flag().load(std::memory_order_relaxed) > 0 && plain && pinned_cfg() < 0) {
-    const int t = igemm_tap_cfg(g, cdim, ncol);
-    if (t >= 0) return t;
-  }
-  int cfg = auto_cfg(M, ncol, Kdim, true);
-  static const int rules = [] {   // SDX_CFG_RULES: bit mask of the corrections below (A/B)
-    const char* e = getenv("SDX_CFG_RULES");
-    return e == nullptr ? 4 : atoi(e);
-  }();
-  if (pinned_cfg() >= 0) return cfg;
-  auto tiles = [&](int c) { return ((M + igemm_tile_m(c) - 1) / igemm_tile_m(c)) * ((ncol + igemm_tile_n(c) - 1) / igemm_tile_n(c)); };
-  if ((rules & 1) && cfg == 6 && tiles(6) < 256) cfg = 4;
-  if ((rules & 2) && dgrad && g.stride == 1 && ncol >= 256 && 2 * Kdim <= ncol) cfg = 2;
-  if ((rules & 4) && dgrad && g.stride > 1 && ncol % 256 == 0 && Kdim * g.stride * g.stride >= 1024) cfg = 6;
-  return cfg;
-}
-
-int auto_cfg(int64_t M, int64_t Ncol, int64_t Kdim, bool fill) {
-  const int pinned = pinned_cfg();
-  if (fill && pinned >= 0) return pinned;
-  const int64_t bm[4] = {128, 256, 64, 64}, bn[4] = {128, 64, 256, 64};
-  const bool long_k = Kdim == 0 || Kdim > 256;
-  const double pen_long[4] = {1.0, 1.04, 1.04, 1.35}, pen_short[4] = {1.0, 1.0, 1.0, 1.05};
-  const double slots[4] = {512, 512, 512, 1280};   // resident blocks chip-wide (LDS/VGPR-limited)
-  int best = 0;
-  double best_s = 1e300;
-  for (int c = 0; c < 4; ++c) {
-    const int64_t mt = (M + bm[c] - 1) / bm[c], nt = (Ncol + bn[c] - 1) / bn[c];
-    const double padded = (double)(mt * bm[c]) * (double)(nt * bn[c]);
-    double f = 1.0;
-    if (fill) {
-      const double tiles = (double)(mt * nt);
-      f = std::ceil(tiles / slots[c]) * slots[c] / tiles;
-    }
-    const double sc = padded * (long_k ? pen_long[c] : pen_short[c]) * f;
-    if (sc < best_s) { best_s = sc; best = c; }
-  }
-  // fwd/dgrad: the 8-wave 128x128 tile (cfg 4, 2x4 waves of 64x32) beats the 4-wave one by
-  // 3-12% on every ResNet-50 shape with a reduction of >= 128 (more waves hide the LDS-DMA
-  // and epilogue latency); on the K=64 layer-1 GEMMs its longer prologue costs more than it
-  // hides. wgrad keeps the 4-wave tiles (its split-K slabs are short). profiles/conv_cfg4_r1.txt
-  if (fill && best == 0 && Kdim >= 128) best = 4;
-  // long-K GEMMs whose output width is a multiple of 256 (layers 3-4): the 8-wave 128x256 tile
-  // on the in-wave pipelined LDS-DMA ring (cfg 6, DEPTH 6) — l3 3x3 fwd/dgrad 41.3 -> 38.1 us,
-  // l4.0.sc dgrad 67.5 -> 64.8 us; it loses on narrower or short-K GEMMs, where one tile per CU
-  // leaves its prologue/epilogue exposed (profiles/conv_core_r4.txt)
-  static const bool d6 = [] {
-    const char* e = getenv("SDX_CONV_D6");
-    return e == nullptr || atoi(e) != 0;
-  }();
-  if (fill && d6 && Ncol % 256 == 0 && Kdim >= 1024) best = 6;
-  return best;
-}
+int auto_cfg(int64_t M, int64_t Ncol, int64_t Kdim, bool fill) { return sdx_plan::auto_cfg(M, Ncol, Kdim, fill, knobs()); }
 
 namespace {
 
@@ -166,24 +71,20 @@ std::vector<torch::Tensor> conv_fwd_impl(torch::Tensor x, torch::Tensor w, int64
   TORCH_CHECK(g.P > 0 && g.Q > 0, "empty output");
   TORCH_CHECK(g.K % 8 == 0, "Cout must be a multiple of 8");
   c10::DeviceGuard dg(x.device());
-  const int64_t M = (int64_t)g.N * g.P * g.Q;
-  if (cfg < 0)
-    cfg = conv_cfg(g, g.C, g.K, M, (int64_t)g.R * g.S * g.C, !in_scale.has_value(), false);
+  const sdx_plan::FwdPlan plan = sdx_plan::plan_fwd(g, cfg, in_scale.has_value(), knobs());
   TORCH_CHECK(!no_out || (want_stats && epi == nullptr), "statistics-only conv: stats, no epilogue");
   auto y = no_out ? torch::Tensor() : torch::empty({g.N, g.P, g.Q, g.K}, x.options());
   torch::Tensor slab;
   float* sp = nullptr;
   if (want_stats) {
-    const int64_t mt = g.stride == 1 ? igemm_conv_mtiles(g, g.C, (int)cfg, M)
-                                     : (M + igemm_tile_m(cfg) - 1) / igemm_tile_m(cfg);
-    slab = torch::empty({mt, 2, g.K}, x.options().dtype(at::kFloat));
+    slab = torch::empty({plan.m_tiles, 2, g.K}, x.options().dtype(at::kFloat));
     sp = slab.data_ptr<float>();
   } else {
     slab = torch::empty({0}, x.options().dtype(at::kFloat));
   }
   const float *isc, *ish;
   in_bn_ptrs(in_scale, in_shift, g.C, &isc, &ish);
-  check_hip(launch_conv_fwd(g, x.data_ptr(), w.data_ptr(), no_out ? nullptr : y.data_ptr(), sp, (int)cfg, cur_stream(),
+  check_hip(launch_conv_fwd(g, x.data_ptr(), w.data_ptr(), no_out ? nullptr : y.data_ptr(), sp, plan.cfg, cur_stream(),
                             isc, ish, epi),
             "conv_fwd");
   return {y, slab};
@@ -243,34 +144,55 @@ struct CatScope {
   CatScope& operator=(const CatScope&) = delete;
 };
 
-torch::Tensor conv_dgrad_impl(torch::Tensor dy, torch::Tensor wt, int64_t H, int64_t W, int64_t stride, int64_t pad,
-                              int64_t cfg, c10::optional<torch::Tensor> out, c10::optional<torch::Tensor> addend,
-                              c10::optional<torch::Tensor> addend_mask, BnBwdStat* bs, int64_t addend_sub = 0) {
+// One data gradient's checked request: geometry, the K-concatenated operand taken from
+// fold_cat() (consumed by this dgrad only) and the plan, computed once for the launches and
+// for the statistics slab
+struct DgradReq {
+  ConvGeom g;
+  FoldCat cat;
+  int64_t cat_ch;
+  sdx_plan::DgradPlan plan;
+};
+DgradReq dgrad_request(const torch::Tensor& dy, const torch::Tensor& wt, int64_t H, int64_t W, int64_t stride,
+                       int64_t pad, int64_t cfg, bool bstat) {
   check_bf16_nhwc(dy, "dy");
   check_bf16_nhwc(wt, "wt");
-  const FoldCat cat = fold_cat();
-  fold_cat() = FoldCat{};   // consumed by this dgrad only
-  const int64_t cat_ch = cat.a2 != nullptr ? cat.a2->size(3) : 0;
-  TORCH_CHECK(wt.size(3) == dy.size(3) + cat_ch, "wt last dim must be Cout (+ the concatenated operand's channels)");
+  DgradReq r{};
+  r.cat = fold_cat();
+  fold_cat() = FoldCat{};
+  const FoldCat& cat = r.cat;
+  r.cat_ch = cat.a2 != nullptr ? cat.a2->size(3) : 0;
+  TORCH_CHECK(wt.size(3) == dy.size(3) + r.cat_ch, "wt last dim must be Cout (+ the concatenated operand's channels)");
   if (cat.a2 != nullptr) {
     check_bf16_nhwc(*cat.a2, "cat a2");
-    TORCH_CHECK(stride == 1 && pad == 0 && wt.size(1) == 1 && wt.size(2) == 1 && !addend.has_value() &&
-                    cat.a2->size(0) == dy.size(0) && cat.a2->size(1) == dy.size(1) && cat.a2->size(2) == dy.size(2),
-                "K-concatenated dgrad: stride-1 1x1, no addend, a2 on dy's pixels");
+    TORCH_CHECK(stride == 1 && pad == 0 && wt.size(1) == 1 && wt.size(2) == 1 && cat.a2->size(0) == dy.size(0) &&
+                    cat.a2->size(1) == dy.size(1) && cat.a2->size(2) == dy.size(2),
+                "K-concatenated dgrad: stride-1 1x1, a2 on dy's pixels");
     TORCH_CHECK(cat.bias->is_cuda() && cat.bias->scalar_type() == at::kFloat && cat.bias->is_contiguous() &&
                     cat.bias->numel() == wt.size(0),
                 "K-concatenated dgrad: fp32 bias [C]");
   }
-  ConvGeom g{};
+  ConvGeom& g = r.g;
   g.N = dy.size(0); g.P = dy.size(1); g.Q = dy.size(2); g.K = dy.size(3);
   g.C = wt.size(0); g.R = wt.size(1); g.S = wt.size(2);
   g.H = H; g.W = W; g.stride = stride; g.pad = pad;
-  TORCH_CHECK((g.H + 2 * pad - g.R) / stride + 1 == g.P && (g.W + 2 * pad - g.S) / stride + 1 == g.Q,
+  TORCH_CHECK(stride >= 1 && (g.H + 2 * pad - g.R) / stride + 1 == g.P && (g.W + 2 * pad - g.S) / stride + 1 == g.Q,
               "dgrad geometry mismatch");
   TORCH_CHECK(g.C % 8 == 0, "Cin must be a multiple of 8");
+  r.plan = sdx_plan::plan_dgrad(g, cfg, (int)r.cat_ch, bstat, knobs());
+  TORCH_CHECK(r.plan.ok, "conv_dgrad: tile config ", r.plan.cfg, " does not run this geometry");
+  return r;
+}
+
+torch::Tensor conv_dgrad_impl(torch::Tensor dy, torch::Tensor wt, const DgradReq& rq,
+                              c10::optional<torch::Tensor> out, c10::optional<torch::Tensor> addend,
+                              c10::optional<torch::Tensor> addend_mask, BnBwdStat* bs, int64_t addend_sub = 0) {
+  const ConvGeom& g = rq.g;
+  const FoldCat& cat = rq.cat;
+  const sdx_plan::DgradPlan& plan = rq.plan;
+  const int64_t cat_ch = rq.cat_ch, stride = g.stride;
+  TORCH_CHECK(cat.a2 == nullptr || !addend.has_value(), "K-concatenated dgrad: no addend");
   c10::DeviceGuard dg(dy.device());
-  const int64_t M = (int64_t)g.N * g.H * g.W / (stride * stride);
-  if (cfg < 0) cfg = conv_cfg(g, g.K, g.C, M, (int64_t)g.R * g.S * (g.K + cat_ch) / (stride * stride), true, true);
   torch::Tensor dx;
   if (out.has_value()) {
     dx = *out;
@@ -315,42 +237,36 @@ torch::Tensor conv_dgrad_impl(torch::Tensor dy, torch::Tensor wt, int64_t H, int
       ce.bias_pre = cat.bias->data_ptr<float>();
       epi = &ce;
     }
-    check_hip(launch_conv_dgrad_class(g, 0, 0, dy.data_ptr(), wt.data_ptr(), dx.data_ptr(), add, (int)cfg,
+    check_hip(launch_conv_dgrad_class(g, 0, 0, dy.data_ptr(), wt.data_ptr(), dx.data_ptr(), add, plan.cfg,
                                       cur_stream(), amask, bs, add ? (int)addend_sub : 0, epi),
               "conv_dgrad");
     return dx;
   }
   // sub-pixel classes: each gets the taps r ≡ ph+pad, s ≡ pw+pad (mod stride); by default all
-  // of them in one launch (SDX_DGRAD_MERGE=0: one launch per class)
-  // SDX_DGRAD_MERGE: 0 one launch per class, 1 merged for every strided dgrad, 2 merged for
-  // strided 3x3 only (default: a strided 1x1 has one non-empty class, whose launch is faster
-  // on its own — profiles/dgrad_merge_r4.txt)
-  static const int merge = [] {
-    const char* e = getenv("SDX_DGRAD_MERGE");
-    return e == nullptr ? 2 : atoi(e);
-  }();
-  if (stride == 2 && (merge == 1 || (merge == 2 && g.R > 1))) {
-    check_hip(launch_conv_dgrad_merged(g, dy.data_ptr(), wt.data_ptr(), dx.data_ptr(), add, (int)cfg, cur_stream(),
-                                       amask, bs, add ? (int)addend_sub : 0),
+  // of them in one launch (plan.merged, SDX_DGRAD_MERGE)
+  if (plan.merged) {
+    check_hip(launch_conv_dgrad_merged(g, plan, dy.data_ptr(), wt.data_ptr(), dx.data_ptr(), add, cur_stream(), amask,
+                                       bs, add ? (int)addend_sub : 0),
               "conv_dgrad(merged classes)");
     return dx;
   }
-  for (int ph = 0; ph < stride; ++ph)
-    for (int pw = 0; pw < stride; ++pw) {
-      // each class reads its taps straight from the full Wt (no per-class weight copy; a
-      // class without taps writes zeros and never reads B)
-      check_hip(launch_conv_dgrad_class(g, ph, pw, dy.data_ptr(), wt.data_ptr(), dx.data_ptr(), add, (int)cfg,
-                                        cur_stream(), amask, bs, add ? (int)addend_sub : 0),
-                "conv_dgrad(class)");
-      if (bs) bs->row0 += conv_dgrad_class_mtiles(g, ph, pw, (int)cfg);
-    }
+  for (int i = 0; i < plan.ncls; ++i) {
+    // each class reads its taps straight from the full Wt (no per-class weight copy; a
+    // class without taps writes zeros and never reads B)
+    const sdx_plan::DgradClass& c = plan.cls[i];
+    check_hip(launch_conv_dgrad_class(g, c.ph, c.pw, dy.data_ptr(), wt.data_ptr(), dx.data_ptr(), add, plan.cfg,
+                                      cur_stream(), amask, bs, add ? (int)addend_sub : 0),
+              "conv_dgrad(class)");
+    if (bs) bs->row0 += c.m_tiles;
+  }
   return dx;
 }
 
 torch::Tensor conv_dgrad(torch::Tensor dy, torch::Tensor wt, int64_t H, int64_t W, int64_t stride, int64_t pad,
                          int64_t cfg, c10::optional<torch::Tensor> out, c10::optional<torch::Tensor> addend,
                          c10::optional<torch::Tensor> addend_mask, int64_t addend_sub = 0) {
-  return conv_dgrad_impl(dy, wt, H, W, stride, pad, cfg, out, addend, addend_mask, nullptr, addend_sub);
+  const DgradReq rq = dgrad_request(dy, wt, H, W, stride, pad, cfg, false);
+  return conv_dgrad_impl(dy, wt, rq, out, addend, addend_mask, nullptr, addend_sub);
 }
 
 // dgrad + fused BN-backward statistics of dx for the BN whose pre-BN tensor is ya (and yb,
@@ -361,6 +277,7 @@ std::vector<torch::Tensor> conv_dgrad_bnstat_impl(torch::Tensor dy, torch::Tenso
                                                   OptT addend_mask, torch::Tensor ya, torch::Tensor ma, OptT yb,
                                                   OptT mb, OptT mask_bits, OptT msc, OptT msh, int64_t addend_sub,
                                                   int store_masked = 0, int64_t extra_rows = 0) {
+  const DgradReq rq = dgrad_request(dy, wt, H, W, stride, pad, cfg, true);
   const int64_t C = wt.size(0);
   // an empty ya: the BN input was never stored (forward-folded BN3) — the epilogue sums
   // Σdz and Σdz·(0 − μ); the caller fills extra_rows rows of the slab with the Σdz·y terms
@@ -395,22 +312,13 @@ std::vector<torch::Tensor> conv_dgrad_bnstat_impl(torch::Tensor dy, torch::Tenso
     bs.msc = msc->data_ptr<float>();
     bs.msh = msh->data_ptr<float>();
   }
-  ConvGeom g{};
-  g.N = dy.size(0); g.P = dy.size(1); g.Q = dy.size(2); g.K = dy.size(3);
-  g.C = C; g.R = wt.size(1); g.S = wt.size(2);
-  g.H = H; g.W = W; g.stride = stride; g.pad = pad;
-  const int64_t M = (int64_t)g.N * g.H * g.W / (stride * stride);
-  const int64_t cat_ch = fold_cat().a2 != nullptr ? fold_cat().a2->size(3) : 0;   // (CatScope)
-  if (cfg < 0) cfg = conv_cfg(g, g.K, g.C, M, (int64_t)g.R * g.S * (g.K + cat_ch) / (stride * stride), true, true);
-  int rows = 0;
-  for (int ph = 0; ph < stride; ++ph)
-    for (int pw = 0; pw < stride; ++pw) rows += conv_dgrad_class_mtiles(g, ph, pw, (int)cfg);
+  const int rows = rq.plan.rows;
   const int ns = yb.has_value() ? 3 : 2;
   auto slab = torch::empty({rows + extra_rows, ns, C}, dy.options().dtype(at::kFloat));
   bs.slab = slab.data_ptr<float>();
   TORCH_CHECK(!store_masked || (mask_bits.has_value() && stride == 1), "store_masked: stride-1 with a ReLU bitmask");
   bs.store_masked = store_masked;
-  auto dx = conv_dgrad_impl(dy, wt, H, W, stride, pad, cfg, out, addend, addend_mask, &bs, addend_sub);
+  auto dx = conv_dgrad_impl(dy, wt, rq, out, addend, addend_mask, &bs, addend_sub);
   return {dx, slab};
 }
 
@@ -443,17 +351,9 @@ void keep_deferred_partial(const torch::Tensor& part) {
 // critical path). A step captured as one hipGraph chain runs them alone, in line, so
 // PretrainEngine.enable_cuda_graph raises it to the whole chip for the capture
 // (wgrad_block_target_set).
-std::atomic<int64_t>& wgrad_block_target_ref() {
-  static std::atomic<int64_t> t{[] {
-    const char* e = getenv("SDX_W3_BLOCKS");
-    return e ? atoll(e) : 128LL;
-  }()};
-  return t;
-}
-int64_t wgrad_block_target() { return wgrad_block_target_ref().load(std::memory_order_relaxed); }
 int64_t wgrad_block_target_set(int64_t n) {
   TORCH_CHECK(n >= 1 && n <= 4096, "block target in [1, 4096]");
-  return wgrad_block_target_ref().exchange(n);
+  return std::exchange(knobs_mut().w3_blocks, (long long)n);
 }
 
 torch::Tensor conv_wgrad(torch::Tensor dy, torch::Tensor x, int64_t R, int64_t S, int64_t stride, int64_t pad,
@@ -469,104 +369,7 @@ torch::Tensor conv_wgrad(torch::Tensor dy, torch::Tensor x, int64_t R, int64_t S
   TORCH_CHECK((g.H + 2 * pad - R) / stride + 1 == g.P && (g.W + 2 * pad - S) / stride + 1 == g.Q,
               "wgrad geometry mismatch");
   c10::DeviceGuard dg(x.device());
-  const int64_t M = g.K, Ncol = (int64_t)R * S * g.C, Kd = (int64_t)g.N * g.P * g.Q;
-  // cfg 9 = the tap-reuse 3x3 kernel (wgrad3x3.hip), which auto (cfg -1) picks for every
-  // shape it supports (SDX_WGRAD3=0: generic implicit GEMM only); cfg -2 = generic auto
-  static const bool w3_on = [] {
-    const char* e = getenv("SDX_WGRAD3");
-    return e == nullptr || atoi(e) != 0;
-  }();
-  const bool w3 = (cfg == 9 || (cfg == -1 && w3_on && splits <= 0)) && !in_scale.has_value() && wgrad3x3_supported(g);
-  TORCH_CHECK(cfg != 9 || w3, "conv_wgrad: cfg 9 needs a pad-1 3x3 conv of stride 1 or 2 on square images with output width in {4,8,16,32}, C,K % 64 == 0");
-  // cfg 10 = the stride-1 1x1 kernel (wgrad1x1.hip), auto-picked for every shape it supports
-  // (SDX_WGRAD1=0: generic only)
-  static const bool w1_on = [] {
-    const char* e = getenv("SDX_WGRAD1");
-    return e == nullptr || atoi(e) != 0;
-  }();
-  const bool w1 = (cfg == 10 || (cfg == -1 && w1_on && splits <= 0)) && !in_scale.has_value() && wgrad1x1_supported(g);
-  TORCH_CHECK(cfg != 10 || w1, "conv_wgrad: cfg 10 needs a 1x1 conv with K,C % 128 == 0 (stride 1, or stride s with H = s*P, W = s*Q), or stride 1 with K or C = 64");
-  // 64-output-channel GEMMs with a wide reduction side (layer-1 3x3: 64 x 576): the 64x256
-  // tile (four 64x64 wave tiles) beats the exact-fit 64x64 one despite its padding, at
-  // ~512 blocks (tools/wgrad_split_probe.py: 145 -> 124 us)
-  static const bool wide64 = [] {
-    const char* e = getenv("SDX_WGRAD_WIDE64");
-    return e == nullptr || atoi(e) != 0;
-  }();
-  // The stage-1 weight gradients (the most pixels) are the last work of the backward: when
-  // they run, the main stream has (almost) nothing left, so the half-chip block target that
-  // keeps the side stream off the critical-path kernels only leaves CUs idle in the step's
-  // tail (profiles: a 390 us gap before the SGD at 256 images/GPU). GEMMs with at least
-  // SDX_W3_TAIL_PIX pixels (2^18 = stage 1 at 128 and 256 images/GPU) get
-  // SDX_W3_TAIL_BLOCKS (default 256) blocks. Default 0 (off): the gap shrinks to 180 us but
-  // the wider stage-1 wgrads slow the concurrent stage-1 dgrads more, 12.43 vs 12.37 ms
-  // (512 blocks: 12.52; same-box A/B, profiles/tail_ab_r4.txt)
-  static const int64_t tail_pix = [] {
-    const char* e = getenv("SDX_W3_TAIL_PIX");
-    return e ? atoll(e) : 0LL;
-  }();
-  static const int64_t tail_blocks = [] {
-    const char* e = getenv("SDX_W3_TAIL_BLOCKS");
-    return e ? atoll(e) : 256LL;
-  }();
-  const bool tail = tail_pix > 0 && Kd >= tail_pix;
-  if (w1) {
-    // as for the 3x3 kernel: SDX_W3_BLOCKS (128) 8-wave blocks, >= 8 steps each
-    const int64_t steps = wgrad1x1_steps(g);
-    if (splits <= 0) {
-      const int64_t target0 = wgrad_block_target();
-      // pixel-pair shapes (HBM-bound, twice the MFMA work per byte): SDX_W1_PAIR_BLOCKS
-      static const int64_t pair_target = [] {
-        const char* e = getenv("SDX_W1_PAIR_BLOCKS");
-        return e ? atoll(e) : 256LL;
-      }();
-      const int64_t target = tail ? tail_blocks : (wgrad1x1_pair_view(g) ? pair_target : target0);
-      splits = std::max<int64_t>(1, target / wgrad1x1_tiles(g));
-      splits = std::min(splits, std::max<int64_t>(1, steps / 8));
-    }
-    const int64_t per = (steps + splits - 1) / splits;
-    splits = (steps + per - 1) / per;
-  } else if (w3) {
-    if (splits <= 0) {
-      // SDX_W3_BLOCKS (default 128) 8-wave blocks, >= 8 steps per split. Standalone, 256
-      // blocks (one per CU) is fastest (tools/w3_sweep.py), but in the training step these
-      // kernels run on the wgrad side stream: a block holds ~416 of a SIMD lane's 512 VGPRs,
-      // so the critical-path kernels (128-VGPR dgrads, the BN reductions) cannot co-reside on
-      // its CU. 128 blocks leave half the CUs to the main stream: step 13.71 -> 13.34 ms at
-      // 256 images/GPU, 8.48 -> 8.20 ms at 128 (profiles/wgrad3x3_r2.txt)
-      const int64_t target0 = wgrad_block_target();
-      const int64_t target = tail ? tail_blocks : target0;
-      const int64_t tiles = wgrad3x3_tiles(g), steps = wgrad3x3_steps(g);
-      splits = std::max<int64_t>(1, target / tiles);
-      splits = std::min(splits, std::max<int64_t>(1, steps / 8));
-    }
-    const int64_t steps = wgrad3x3_steps(g);
-    const int64_t per = (steps + splits - 1) / splits;
-    splits = (steps + per - 1) / per;
-  } else {
-    if (wide64 && cfg < 0 && splits <= 0 && M <= 64 && Ncol >= 512) cfg = 2;
-    if (cfg < 0) cfg = auto_cfg(M, Ncol);
-    if (splits <= 0) {
-      const int64_t tiles = ((M + igemm_tile_m(cfg) - 1) / igemm_tile_m(cfg)) *
-                            ((Ncol + igemm_tile_n(cfg) - 1) / igemm_tile_n(cfg));
-      // SDX_WGRAD_TARGET: block target of the generic wgrad split heuristic (default 512)
-      static const int64_t gen_target = [] {
-        const char* e = getenv("SDX_WGRAD_TARGET");
-        return e ? atoll(e) : 512LL;
-      }();
-      splits = std::max<int64_t>(1, gen_target / tiles);
-      const int64_t max_splits = std::max<int64_t>(1, Kd / 512);   // >= 8 K-tiles per split
-      splits = std::min(splits, max_splits);
-      // bound the fp32 partial slab to ~64 MiB, and to ~16 MiB / 256 splits for 1x1 GEMMs with
-      // a small output (M*Ncol <= 64K: the layer-1/2 pointwise convs), where the slab round
-      // trip outweighs the extra splits' parallelism (profiles/wgrad_sweep_r1.txt: 83 -> 67 us
-      // on the 256x64 layer-1 GEMMs; the 3x3 and larger GEMMs keep more splits)
-      const bool small_1x1 = R == 1 && S == 1 && M * Ncol <= 65536;
-      splits = std::min<int64_t>(splits, std::max<int64_t>(1, (small_1x1 ? (4LL << 20) : (16LL << 20)) / (M * Ncol)));
-      if (small_1x1) splits = std::min<int64_t>(splits, 256);
-    }
-    splits = conv_wgrad_splits(g, (int)cfg, (int)splits);
-  }
+  const int64_t M = g.K, Ncol = (int64_t)R * S * g.C;
   torch::Tensor dw;
   if (out.has_value()) {
     dw = *out;
@@ -581,27 +384,25 @@ torch::Tensor conv_wgrad(torch::Tensor dy, torch::Tensor x, int64_t R, int64_t S
   }
   const float *isc, *ish;
   in_bn_ptrs(in_scale, in_shift, g.C, &isc, &ish);
+  // the kernel family, tile config, splits and slab size: sdx_plan::plan_wgrad
+  const sdx_plan::WgradPlan plan = sdx_plan::plan_wgrad(g, splits, cfg, accumulate, in_scale.has_value(), knobs());
+  TORCH_CHECK(cfg != 9 || plan.ok, "conv_wgrad: cfg 9 needs a pad-1 3x3 conv of stride 1 or 2 on square images with output width in {4,8,16,32}, C,K % 64 == 0");
+  TORCH_CHECK(cfg != 10 || plan.ok, "conv_wgrad: cfg 10 needs a 1x1 conv with K,C % 128 == 0 (stride 1, or stride s with H = s*P, W = s*Q), or stride 1 with K or C = 64");
+  TORCH_CHECK(plan.ok, "conv_wgrad: no such tile config: ", cfg);
   torch::Tensor part;
-  const int64_t slices = w1 ? wgrad1x1_slices(g, (int)splits) : splits;
-  if (slices > 1 || accumulate)
-    part = torch::empty({slices * M * Ncol}, x.options().dtype(at::kFloat));
-  if (w1) {
-    check_hip(launch_wgrad1x1(g, dy.data_ptr(), x.data_ptr(), part.defined() ? part.data_ptr<float>() : nullptr,
-                              dw.data_ptr<float>(), (int)splits, accumulate ? 1 : 0, cur_stream()),
+  if (plan.slab_elems > 0) part = torch::empty({plan.slab_elems}, x.options().dtype(at::kFloat));
+  float* pp = part.defined() ? part.data_ptr<float>() : nullptr;
+  const int acc = accumulate ? 1 : 0;
+  if (plan.family == sdx_plan::WGRAD_1X1)
+    check_hip(launch_wgrad1x1(g, plan, dy.data_ptr(), x.data_ptr(), pp, dw.data_ptr<float>(), acc, cur_stream()),
               "conv_wgrad(1x1)");
-    keep_deferred_partial(part);
-    return dw;
-  }
-  if (w3) {
-    check_hip(launch_wgrad3x3(g, dy.data_ptr(), x.data_ptr(), part.defined() ? part.data_ptr<float>() : nullptr,
-                              dw.data_ptr<float>(), (int)splits, accumulate ? 1 : 0, cur_stream()),
+  else if (plan.family == sdx_plan::WGRAD_3X3)
+    check_hip(launch_wgrad3x3(g, plan, dy.data_ptr(), x.data_ptr(), pp, dw.data_ptr<float>(), acc, cur_stream()),
               "conv_wgrad(3x3)");
-    keep_deferred_partial(part);
-    return dw;
-  }
-  check_hip(launch_conv_wgrad(g, dy.data_ptr(), x.data_ptr(), part.defined() ? part.data_ptr<float>() : nullptr,
-                              dw.data_ptr<float>(), (int)cfg, (int)splits, accumulate ? 1 : 0, cur_stream(), isc, ish),
-            "conv_wgrad");
+  else
+    check_hip(launch_conv_wgrad(g, plan, dy.data_ptr(), x.data_ptr(), pp, dw.data_ptr<float>(), acc, cur_stream(), isc,
+                                ish),
+              "conv_wgrad");
   keep_deferred_partial(part);
   return dw;
 }
@@ -1087,8 +888,7 @@ hipEvent_t next_event() {
     // point drops from ~7.0 to ~5.0 us (48 forks per step) and the step by 0.11 ms (3/3
     // same-box rounds, profiles/event_fence_r6.txt). SDX_EV_FENCE: 0 = the default fence,
     // 1 = hipEventDisableSystemFence (default), 2 = hipEventReleaseToDevice (-0.03 ms)
-    const char* ef = getenv("SDX_EV_FENCE");
-    const int fm = ef ? atoi(ef) : 1;
+    const int fm = (int)sdx_plan::env_int("SDX_EV_FENCE", 1);
     const unsigned fl = hipEventDisableTiming | (fm == 1 ? hipEventDisableSystemFence : 0u) |
                         (fm == 2 ? hipEventReleaseToDevice : 0u);
     pool.resize(512);
@@ -1145,28 +945,19 @@ std::vector<torch::Tensor> bn_bwd_coef_slab(int64_t comm, torch::Tensor slab, do
 }
 
 bool sub_addend_enabled() {
-  static const bool on = [] {
-    const char* e = getenv("SDX_SUB_ADDEND");
-    return e == nullptr || atoi(e) != 0;
-  }();
+  static const bool on = sdx_plan::env_flag("SDX_SUB_ADDEND", true);
   return on;
 }
 
 bool dgrad_bnstat_enabled() {
-  static const bool on = [] {
-    const char* e = getenv("SDX_DGRAD_BNSTAT");
-    return e == nullptr || atoi(e) != 0;
-  }();
+  static const bool on = sdx_plan::env_flag("SDX_DGRAD_BNSTAT", true);
   return on;
 }
 
 // SDX_SPLITK_MERGE=0 (or splitk_merge_set(False)): one split-K reduction launch per weight
 // gradient (round-3 behaviour)
 std::atomic<int>& splitk_merge_flag() {
-  static std::atomic<int> on{[] {
-    const char* e = getenv("SDX_SPLITK_MERGE");
-    return e == nullptr || atoi(e) != 0 ? 1 : 0;
-  }()};
+  static std::atomic<int> on{sdx_plan::env_flag("SDX_SPLITK_MERGE", true) ? 1 : 0};
   return on;
 }
 bool splitk_merge_enabled() { return splitk_merge_flag().load(std::memory_order_relaxed) != 0; }
@@ -1296,10 +1087,7 @@ struct FoldOps {
   bool cat = false;
 };
 bool fold_cat_enabled() {
-  static const bool on = [] {
-    const char* e = getenv("SDX_FOLD_CAT");
-    return e == nullptr || atoi(e) != 0;
-  }();
+  static const bool on = sdx_plan::env_flag("SDX_FOLD_CAT", true);
   return on;
 }
 FoldOps fold_dgrad_operands(const torch::Tensor& coef, const torch::Tensor& w3, const torch::Tensor& wt3,
@@ -1317,7 +1105,7 @@ FoldOps fold_dgrad_operands(const torch::Tensor& coef, const torch::Tensor& w3, 
   FoldOps r;
   r.bias = torch::empty({K3}, coef.options());
   const float* cs = gram != nullptr ? gram[1].data_ptr<float>() : nullptr;
-  if (fold_cat_enabled() && conv_dgrad_cat_supported(gd, (int)K3)) {
+  if (fold_cat_enabled() && sdx_plan::dgrad_cat_supported(gd, (int)K3, knobs())) {
     r.cat = true;
     r.w = torch::empty({K3, 1, 1, C3 + K3}, w3.options());
     uint16_t* wc = reinterpret_cast<uint16_t*>(r.w.data_ptr());
@@ -1385,7 +1173,7 @@ std::vector<torch::Tensor> block_fwd(torch::Tensor x, std::vector<torch::Tensor>
     const int64_t M = (int64_t)gs.N * gs.P * gs.Q;
     const int cfg = auto_cfg(M, gs.K, gs.C, true);
     ys_side = torch::empty({gs.N, gs.P, gs.Q, gs.K}, x.options());
-    slab_side = torch::empty({(M + igemm_tile_m(cfg) - 1) / igemm_tile_m(cfg), 2, gs.K}, x.options().dtype(at::kFloat));
+    slab_side = torch::empty({sdx_plan::cdiv(M, sdx_plan::tile_m(cfg)), 2, gs.K}, x.options().dtype(at::kFloat));
     hipEvent_t fork = next_event();
     hipStream_t ss = reinterpret_cast<hipStream_t>(side);
     check_hip(hipEventRecord(fork, cur_stream()), "hipEventRecord");
@@ -1408,7 +1196,7 @@ std::vector<torch::Tensor> block_fwd(torch::Tensor x, std::vector<torch::Tensor>
   // identity blocks: the residual is x (stride 1, same width); projection blocks: the
   // shortcut's pre-BN output ys, normalised in the same epilogue
   fold_fwd = fold_fwd && bottleneck && training && w[2].size(1) == 1 && w[2].size(2) == 1 &&
-             (proj || (stride == 1 && w[2].size(0) == x.size(3))) && conv_fwd_bnapply_supported();
+             (proj || (stride == 1 && w[2].size(0) == x.size(3))) && sdx_plan::fwd_bnapply_supported(knobs());
   torch::Tensor o, ys;
   // the projection shortcut's output and BN statistics (joins the side stream if it ran there)
   auto shortcut = [&] {
@@ -1735,42 +1523,97 @@ torch::Tensor syncbn_exchange_sums(int64_t comm, torch::Tensor slab) {
 
 }  // namespace
 
+// host-only: no GPU call, no allocation (the plan functions of conv_plan.h under knobs())
+pybind11::object conv_plan(int64_t N, int64_t H, int64_t W, int64_t C, int64_t K, int64_t R, int64_t S, int64_t stride,
+                           int64_t pad, bool dgrad, bool full, std::string kind, bool in_bn, bool bnstat,
+                           int64_t cat_ch, int64_t splits, int64_t cfg, bool accumulate) {
+  namespace py = pybind11;
+  TORCH_CHECK(stride >= 1 && R >= 1 && S >= 1, "conv_plan: bad geometry");
+  ConvGeom g{};
+  g.N = (int)N; g.H = (int)H; g.W = (int)W; g.C = (int)C; g.K = (int)K; g.R = (int)R; g.S = (int)S;
+  g.stride = (int)stride; g.pad = (int)pad;
+  g.P = (g.H + 2 * g.pad - g.R) / g.stride + 1;
+  g.Q = (g.W + 2 * g.pad - g.S) / g.stride + 1;
+  if (kind.empty()) kind = dgrad ? "dgrad" : "fwd";
+  auto tap_list = [](bool tap, const sdx_plan::TapGeom& t) {
+    py::list l;
+    const int v[8] = {t.t_rw, t.t_rs, t.t_imgs, t.t_is, t.t_hp, t.t_nhp, t.t_ky, t.t_nch};
+    for (int i = 0; i < 8; ++i) l.append(tap ? v[i] : 0);
+    return l;
+  };
+  py::dict d;
+  if (kind == "fwd") {
+    const sdx_plan::FwdPlan p = sdx_plan::plan_fwd(g, full ? cfg : -1, in_bn, knobs());
+    if (!full) return py::make_tuple(p.cfg, p.m_tiles);
+    py::list dep, one, grid;
+    dep.append(p.depth); one.append(p.one ? 1 : 0); grid.append(p.m_tiles * p.n_tiles);
+    d["cfg"] = p.cfg; d["mt"] = p.m_tiles; d["nt"] = p.n_tiles; d["ok"] = p.ok;
+    d["depth"] = dep; d["one"] = one; d["grid"] = grid; d["tap"] = tap_list(p.tap && p.ok, p.tg);
+    return d;
+  }
+  if (kind == "dgrad") {
+    const sdx_plan::DgradPlan p = sdx_plan::plan_dgrad(g, full ? cfg : -1, (int)cat_ch, bnstat, knobs());
+    if (!full) return py::make_tuple(p.cfg, g.stride == 1 ? (int64_t)p.rows : (int64_t)-1);
+    py::list dep, one, grid, cmt, mmt;
+    const int launches = p.merged ? (p.ncls > 0 ? 1 : 0) : p.ncls;
+    for (int i = 0; i < launches; ++i) {
+      dep.append(p.depth[i]); one.append(p.one[i] ? 1 : 0);
+      grid.append(p.merged ? p.grid : p.cls[i].m_tiles * p.n_tiles);
+    }
+    for (int ph = 0; ph < g.stride; ++ph)      // per (ph, pw), 0 for an empty class
+      for (int pw = 0; pw < g.stride; ++pw) {
+        int mt = 0;
+        for (int i = 0; i < p.ncls; ++i)
+          if (p.cls[i].ph == ph && p.cls[i].pw == pw) mt = p.cls[i].m_tiles;
+        cmt.append(mt);
+      }
+    if (p.merged)
+      for (int i = 0; i < p.ncls; ++i) mmt.append(p.cls[i].m_tiles);   // the kernel's class order
+    d["cfg"] = p.cfg; d["mt"] = p.rows; d["nt"] = p.n_tiles; d["ok"] = p.ok;
+    d["merged"] = p.merged; d["class_mt"] = cmt; d["merged_mt"] = mmt;
+    d["depth"] = dep; d["one"] = one; d["grid"] = grid; d["tap"] = tap_list(p.tap && p.ok, p.tg);
+    return d;
+  }
+  TORCH_CHECK(kind == "wgrad" && full, "conv_plan: kind is fwd, dgrad or wgrad (wgrad: full=True)");
+  const sdx_plan::WgradPlan p = sdx_plan::plan_wgrad(g, splits, cfg, accumulate, in_bn, knobs());
+  TORCH_CHECK(p.ok, "conv_plan: cfg ", cfg, " does not run this weight gradient");
+  static const char* const w1n[] = {"plain", "pipe", "pipe_gen", "big"};
+  static const char* const w3n[] = {"plain", "pad", "s2", "s2pad"};
+  const bool w1 = p.family == sdx_plan::WGRAD_1X1, w3 = p.family == sdx_plan::WGRAD_3X3;
+  d["family"] = w1 ? "1x1" : w3 ? "3x3" : "generic";
+  d["variant"] = w1 ? w1n[p.w1.kind] : w3 ? w3n[p.w3.kind] : "";
+  d["cfg"] = p.cfg; d["steps"] = p.steps; d["per"] = p.per; d["splits"] = p.splits;
+  d["tiles"] = p.tiles; d["slices"] = p.slices; d["slab_elems"] = p.slab_elems; d["direct"] = p.direct;
+  d["grid"] = p.grid; d["depth"] = p.depth; d["bn"] = w1 ? p.w1.bn : 0; d["pairs"] = w1 && p.w1.pairs ? 1 : 0;
+  d["slot"] = w3 ? p.w3.slot : 0; d["ok"] = true;
+  return d;
+}
+
 void register_conv_bn(pybind11::module& m) {
   m.def("conv_fwd_bias", &conv_fwd_bias,
         "implicit-GEMM conv forward with a per-channel fp32 bias (+ReLU) epilogue (eval-mode folded BN)",
         pybind11::arg("x"), pybind11::arg("w"), pybind11::arg("stride"), pybind11::arg("pad"), pybind11::arg("bias"),
         pybind11::arg("relu"));
-  m.def("wgrad1x1_pairs_set", [](int64_t on) { return (int64_t)wgrad1x1_pairs_set((int)on); },
+  m.def("wgrad1x1_pairs_set", [](int64_t on) { return (int64_t)std::exchange(knobs_mut().w1_pairs, on ? 1 : 0); },
         "pixel-pair 1x1 wgrad for 64-channel sides on (1) / off (0); returns the previous value", pybind11::arg("on"));
-  m.def("igemm_one_k_set", [](int64_t mode, int64_t k) { return (int64_t)igemm_one_k_set((int)mode, (int)k); },
+  m.def("igemm_one_k_set", [](int64_t mode, int64_t k) { return (int64_t)std::exchange(knobs_mut().one_k[mode == 0 ? 0 : 1], (int)k); },
         "longest GEMM reduction on the single-stage LDS-DMA loop (mode 0 fwd, 1 dgrad); returns the previous limit",
         pybind11::arg("mode"), pybind11::arg("k"));
   m.def("wgrad_block_target_set", &wgrad_block_target_set,
         "block target of the dedicated 1x1/3x3 wgrad kernels' split heuristic (SDX_W3_BLOCKS); returns the previous value",
         pybind11::arg("n"));
-  m.def("wgrad1x1_big_set", [](int64_t on) { return (int64_t)wgrad1x1_big_set((int)on); },
+  m.def("wgrad1x1_big_set", [](int64_t mode) { return (int64_t)std::exchange(knobs_mut().w1_big, mode < 0 ? 0 : mode > 2 ? 2 : (int)mode); },
         "256-row LDS-DMA 1x1 wgrad kernel: 0 off, 1 long-split shapes (default), 2 every eligible shape; returns the previous value",
         pybind11::arg("mode"));
-  m.def("conv_plan", [](int64_t N, int64_t H, int64_t W, int64_t C, int64_t K, int64_t R, int64_t S, int64_t stride,
-                        int64_t pad, bool dgrad) {
-    // host-only: the tile config auto dispatch picks for a plain fwd / dgrad and the M-tile
-    // count of its statistics slab (padded-row tap tiles count virtual rows)
-    ConvGeom g{};
-    g.N = (int)N; g.H = (int)H; g.W = (int)W; g.C = (int)C; g.K = (int)K; g.R = (int)R; g.S = (int)S;
-    g.stride = (int)stride; g.pad = (int)pad;
-    g.P = (g.H + 2 * g.pad - g.R) / g.stride + 1;
-    g.Q = (g.W + 2 * g.pad - g.S) / g.stride + 1;
-    const int64_t M = dgrad ? N * H * W : (int64_t)g.N * g.P * g.Q;
-    const int cdim = dgrad ? g.K : g.C, ncol = dgrad ? g.C : g.K;
-    const int cfg = dgrad ? conv_cfg(g, cdim, ncol, M, (int64_t)R * S * K / (stride * stride), true, true)
-                          : conv_cfg(g, cdim, ncol, M, (int64_t)R * S * C, true, false);
-    const int64_t mt = dgrad ? (g.stride == 1 ? conv_dgrad_class_mtiles(g, 0, 0, cfg) : -1)
-                             : (g.stride == 1 ? igemm_conv_mtiles(g, g.C, cfg, M)
-                                              : (M + igemm_tile_m(cfg) - 1) / igemm_tile_m(cfg));
-    return pybind11::make_tuple(cfg, mt);
-  }, "host-only dispatch plan of a plain conv: (tile config, statistics-slab M-tiles; -1 for strided dgrads)",
+  m.def("conv_plan", &conv_plan,
+        "host-only dispatch plan of a conv pass under the current knobs. Positional call: (tile config, "
+        "statistics-slab M-tiles; -1 for strided dgrads) of a plain fwd / dgrad. full=True: the whole plan of "
+        "kind 'fwd' | 'dgrad' | 'wgrad' as a dict (tests/test_conv_plan.py, tools/conv_plan_golden.py)",
         pybind11::arg("N"), pybind11::arg("H"), pybind11::arg("W"), pybind11::arg("C"), pybind11::arg("K"),
-        pybind11::arg("R"), pybind11::arg("S"), pybind11::arg("stride"), pybind11::arg("pad"), pybind11::arg("dgrad"));
+        pybind11::arg("R"), pybind11::arg("S"), pybind11::arg("stride"), pybind11::arg("pad"), pybind11::arg("dgrad"),
+        pybind11::arg("full") = false, pybind11::arg("kind") = "", pybind11::arg("in_bn") = false,
+        pybind11::arg("bnstat") = false, pybind11::arg("cat_ch") = 0, pybind11::arg("splits") = 0,
+        pybind11::arg("cfg") = -1, pybind11::arg("accumulate") = false);
   m.def("tap3_set", &tap3_set,
         "tap-reuse 3x3 conv loop on (1) / off (0) for auto tile selection; returns the previous value",
         pybind11::arg("on"));

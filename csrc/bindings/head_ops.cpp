@@ -138,7 +138,7 @@ torch::Tensor gemm_dgrad(const torch::Tensor& dy, const torch::Tensor& wt, int64
   TORCH_CHECK(!out_f32 && bias_sink != nullptr, "masked dgrad: bf16 output with a bias sink");
   check_2d(*relu_ref, at::kBFloat16, "relu_ref");
   TORCH_CHECK(relu_ref->size(0) == rows && relu_ref->size(1) == in, "relu_ref shape");
-  const int64_t mt = conv_dgrad_class_mtiles(g, 0, 0, cfg);
+  const int64_t mt = sdx_plan::conv_mtiles(g, g.K, cfg, rows, sdx_plan::knobs());
   auto slab = torch::empty({mt, 2, in}, dy.options().dtype(at::kFloat));
   BnBwdStat bs{};
   bs.slab = slab.data_ptr<float>();

@@ -184,8 +184,7 @@ int64_t xgmi_emu_create(int64_t world, int64_t cap, double timeout_s) {
   auto a = std::make_unique<Arena>();
   a->emulated = true;
   {
-    const char* e = getenv("SDX_SYNCBN_EMU_SOLO");
-    a->solo = e != nullptr && atoi(e) != 0;
+    a->solo = sdx_plan::env_flag("SDX_SYNCBN_EMU_SOLO", false);
     // a timing diagnostic only (tools/syncbn_latency.py): the W-1 other slots are summed
     // although no rank wrote them, so BN statistics of a training run are wrong under it
     if (a->solo)

@@ -6,6 +6,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "conv_plan.h"
+
 // ---- selftest -------------------------------------------------------------------
 hipError_t launch_mfma16_selftest(const void* A, const void* B, float* C, hipStream_t s);
 
@@ -55,13 +57,8 @@ hipError_t launch_bnfold_rowdot(const float* G, const void* w, int C, int K, int
 hipError_t launch_bnfold_colsum(const void* x, long rows, int K, float* partial, float* cs, hipStream_t s);
 
 // ---- implicit-GEMM convolution (igemm.hip) ------------------------------------
-struct ConvGeom {
-  int N, H, W, C;   // input NHWC
-  int K;            // output channels
-  int R, S;         // filter
-  int P, Q;         // output spatial
-  int stride, pad;
-};
+// (ConvGeom and every dispatch decision — tile config, main loop, splits, slab rows — live in
+// conv_plan.h; the launchers below take the plan or call the same plan functions)
 // DGRAD epilogue BatchNorm-backward statistics of the stored dx (= the output gradient of
 // the BN whose input the conv read): per M-tile Σd·m, Σd·m·(ya−μa) [, Σd·m·(yb−μb)] with
 // m the ReLU mask — bitmask bit (mask), or ya·msc + msh > 0 (msc/msh), or 1 — written to
@@ -104,43 +101,31 @@ struct GemmEpi {
   int cat_ch;
   const float* bias_pre;
 };
-bool conv_dgrad_cat_supported(const ConvGeom& g, int cat_ch);
-bool conv_fwd_bnapply_supported();
-int igemm_tile_m(int cfg);
 // diagnostic main-loop timeline (SDX_IGEMM_TRACE=1): block 0, waves 0 and 4, s_memtime stamps
 int igemm_trace_slots();
 hipError_t igemm_trace_copy(unsigned long long* host, hipStream_t s);
-int igemm_tile_n(int cfg);
-// tap-reuse 3x3 tile config (11-13) for a pad-1 stride-1 3x3 conv whose reduction runs over
-// cdim channels and whose output has ncol channels (DGRAD: cdim = K, ncol = C), or -1
-int igemm_tap_cfg(const ConvGeom& g, int cdim, int ncol);
 // in_scale/in_shift (optional, [C] fp32): fused BN+ReLU prologue on the input activation
 hipError_t launch_conv_fwd(const ConvGeom& g, const void* x, const void* w, void* y, float* stats, int cfg,
                            hipStream_t s, const float* in_scale = nullptr, const float* in_shift = nullptr,
                            const GemmEpi* epi = nullptr);
-// strided dgrad = stride² sub-pixel classes; wt = the full Wt [C][R][S][K] (each class reads
-// its taps r0::st, s0::st in place)
-void conv_dgrad_class(const ConvGeom& g, int ph, int pw, int* r0, int* nr, int* s0, int* ns, int* Hc, int* Wc);
+// strided dgrad = stride² sub-pixel classes (sdx_plan::dgrad_class); wt = the full Wt
+// [C][R][S][K] (each class reads its taps r0::st, s0::st in place)
 // addend (optional, may alias dx): bf16 tensor of dx's shape added in the epilogue
 hipError_t launch_conv_dgrad_class(const ConvGeom& g, int ph, int pw, const void* dy, const void* wt, void* dx,
                                    const void* addend, int cfg, hipStream_t s, const void* addend_mask = nullptr,
                                    const BnBwdStat* bstat = nullptr, int addend_sub = 0,
                                    const GemmEpi* epi = nullptr);
-// every sub-pixel class of a strided dgrad (stride 2) in ONE launch; bstat->row0 = the first
-// class's slab row (the classes' rows follow in the kernel's class order)
-hipError_t launch_conv_dgrad_merged(const ConvGeom& g, const void* dy, const void* wt, void* dx, const void* addend,
-                                    int cfg, hipStream_t s, const void* addend_mask = nullptr,
+// every sub-pixel class of a strided dgrad (stride 2) in ONE launch (plan.merged);
+// bstat->row0 = the first class's slab row (the classes' rows follow in the plan's class order)
+hipError_t launch_conv_dgrad_merged(const ConvGeom& g, const sdx_plan::DgradPlan& plan, const void* dy, const void* wt,
+                                    void* dx, const void* addend, hipStream_t s, const void* addend_mask = nullptr,
                                     const BnBwdStat* bstat = nullptr, int addend_sub = 0);
-// M-tiles of one sub-pixel class launch (= its slab rows with a BnBwdStat)
-// statistics-slab rows (M-tiles) of a stride-1 fwd / dgrad conv with reduction channels cdim
-// under tile config cfg (padded-row tap tiles count virtual rows)
-int64_t igemm_conv_mtiles(const ConvGeom& g, int cdim, int cfg, int64_t M);
-int conv_dgrad_class_mtiles(const ConvGeom& g, int ph, int pw, int cfg);
-int conv_wgrad_splits(const ConvGeom& g, int cfg, int splits);
-// partial: fp32 [splits][K][R*S*C] workspace (unused when splits == 1 and !accumulate)
-hipError_t launch_conv_wgrad(const ConvGeom& g, const void* dy, const void* x, float* partial, float* dw, int cfg,
-                             int splits, int accumulate, hipStream_t s, const float* in_scale = nullptr,
-                             const float* in_shift = nullptr);
+// The weight-gradient launchers take the plan of sdx_plan::plan_wgrad(g, ...) for the same g and
+// accumulate (hipErrorInvalidValue for another family's plan).
+// partial: fp32 plan.slab_elems workspace ([slices][K][R*S*C]; unused when plan.direct)
+hipError_t launch_conv_wgrad(const ConvGeom& g, const sdx_plan::WgradPlan& plan, const void* dy, const void* x,
+                             float* partial, float* dw, int accumulate, hipStream_t s,
+                             const float* in_scale = nullptr, const float* in_shift = nullptr);
 // dW (+)= Σ_split partial[split] (fp32 [splits][n4*4]), deterministic order
 hipError_t launch_splitk_reduce(const float* partial, int splits, long n4, float* dw, int accumulate, hipStream_t s);
 // Deferral of the split-K reductions launched on stream s (this host thread): they are queued
@@ -150,32 +135,12 @@ void splitk_defer_begin(hipStream_t s);
 bool splitk_deferring(hipStream_t s);
 hipError_t splitk_flush();
 void splitk_defer_cancel();   // drop the queue (error paths)
-// Tap-reuse 3x3 wgrad (wgrad3x3.hip): stride 1 or 2, pad 1, output width in {4,8,16,32}, C,K % 64 == 0.
-// partial: fp32 [splits][K][9C] (unused when splits == 1 and !accumulate)
-bool wgrad3x3_supported(const ConvGeom& g);
-int wgrad3x3_tiles(const ConvGeom& g);
-int wgrad3x3_steps(const ConvGeom& g);
-hipError_t launch_wgrad3x3(const ConvGeom& g, const void* dy, const void* x, float* partial, float* dw, int splits,
-                           int accumulate, hipStream_t s);
-// 1x1 wgrad (wgrad1x1.hip): K % 128 == 0, C % 128 == 0, N*H*W % 32 == 0 (stride 1 or a
-// whole-subgrid strided shortcut), or stride 1 with a 64-channel side (pixel pairs, N*H*W % 64).
-// partial: fp32 [wgrad1x1_slices(g, splits)][K][C] (unused when splits == 1, !accumulate and
-// no pixel pairs)
-bool wgrad1x1_supported(const ConvGeom& g);
-int wgrad1x1_tiles(const ConvGeom& g);
-int wgrad1x1_steps(const ConvGeom& g);
-int wgrad1x1_slices(const ConvGeom& g, int splits);
-bool wgrad1x1_pair_view(const ConvGeom& g);
-// runtime switch of the pixel-pair view (tests / A/B); returns the previous value
-int wgrad1x1_pairs_set(int on);
-// the 256-row LDS-DMA kernel: 0 off, 1 long-split shapes only (default), 2 every eligible
-// shape (SDX_W1_BIG); returns the previous setting
-int wgrad1x1_big_set(int mode);
-// longest GEMM reduction on the single-stage LDS-DMA loop (mode 0 forward, 1 data gradient;
-// SDX_IGEMM_ONE_K / _DGRAD); returns the previous limit
-int igemm_one_k_set(int mode, int k);
-hipError_t launch_wgrad1x1(const ConvGeom& g, const void* dy, const void* x, float* partial, float* dw, int splits,
-                           int accumulate, hipStream_t s);
+// Tap-reuse 3x3 wgrad (wgrad3x3.hip; sdx_plan::w3_supported). partial: fp32 [splits][K][9C]
+hipError_t launch_wgrad3x3(const ConvGeom& g, const sdx_plan::WgradPlan& plan, const void* dy, const void* x,
+                           float* partial, float* dw, int accumulate, hipStream_t s);
+// 1x1 wgrad (wgrad1x1.hip; sdx_plan::w1_supported). partial: fp32 [plan.slices][K][C]
+hipError_t launch_wgrad1x1(const ConvGeom& g, const sdx_plan::WgradPlan& plan, const void* dy, const void* x,
+                           float* partial, float* dw, int accumulate, hipStream_t s);
 
 // ---- BatchNorm (bn.hip) ---------------------------------------------------------
 // Per-channel finalize (forward) and coefficient (backward) arguments, evaluated either by

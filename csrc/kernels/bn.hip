@@ -600,8 +600,7 @@ int ew_grid(long n8, bool bwd = false) {
   // SDX_EW_BLOCKS overrides the cap, SDX_EW_BLOCKS_BWD that of bn_bwd_apply alone; rounded
   // to a multiple of 8 blocks (A/B knobs)
   auto env_cap = [](const char* name, long dflt) {
-    const char* e = getenv(name);
-    const long v = e ? atol(e) : 0;
+    const long v = (long)sdx_plan::env_int(name, 0);
     return v >= 8 ? v / 8 * 8 : dflt;
   };
   static const long cap_fwd = env_cap("SDX_EW_BLOCKS", 2048L);
@@ -619,7 +618,7 @@ int col_reduce_gy(int rows) {
   // balance the per-block row loop (rows/gy/4 trips) against the final combine (gy/4 loads);
   // SDX_CR_GY scales the sqrt(rows) rule (A/B knob)
   static const double scale = [] {
-    const char* e = getenv("SDX_CR_GY");
+    const char* e = sdx_plan::env_str("SDX_CR_GY");
     const double v = e ? atof(e) : 0.0;
     return v > 0.0 ? v : 0.5;
   }();

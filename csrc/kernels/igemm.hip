@@ -27,8 +27,6 @@
 // (per-M-tile Σy, Σy² of the stored values → one slab row, reduced in fp64 by
 // bn_stats_reduce). WGRAD writes an fp32 partial slab per K-split (deterministic; reduced
 // by igemm_splitk_reduce), never atomics. Block→tile order is XCD-aware.
-#include <atomic>
-
 #include "common.h"
 #include "launchers.h"
 
@@ -38,6 +36,7 @@ namespace {
 
 enum { MODE_FWD = 0, MODE_DGRAD = 1, MODE_WGRAD = 2 };
 constexpr int BK = 64;
+static_assert(BK == sdx_plan::kBK && MODE_WGRAD == sdx_plan::MODE_WGRAD, "conv_plan.h plans this K-tile");
 #ifndef SDX_PRIO_HALF
 #define SDX_PRIO_HALF 1
 #endif
@@ -163,10 +162,7 @@ struct IgemmParams {
   int t_rs, t_is, t_ky, t_hp, t_nhp, t_nch, t_imgs, t_rw;
 };
 
-// DEPTH 7 / 8 halo buffer size in KiB: the largest window a BM-row tile needs over the
-// supported image widths (BM = 256: 4 images of 8x8 = 4·10·10 pixels = 50 KiB at 64
-// channels; BM = 128: 8 images of 4x4 = 8·6·6 pixels = 36 KiB)
-constexpr int tap_halo_kb(int bm) { return bm == 256 ? 50 : 36; }
+using sdx_plan::tap_halo_kb;   // DEPTH 7 / 8 halo buffer size in KiB
 
 typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
 
@@ -1641,73 +1637,15 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
   }
 }
 
-// register-prefetch depth of the K loop (SDX_IGEMM_DEPTH=1|2, default 2)
-int igemm_depth() {
-  static const int d = [] {
-    const char* e = getenv("SDX_IGEMM_DEPTH");
-    return (e && e[0] == '1') ? 1 : 2;
-  }();
-  return d;
-}
-
-// LDS-DMA operand staging: 0 off, 1 FWD/DGRAD (default), 2 FWD/DGRAD/WGRAD
-int igemm_glds() {
-  static const int a = [] {
-    const char* e = getenv("SDX_IGEMM_GLDS");
-    return e ? atoi(e) : 1;
-  }();
-  return a;
-}
-
+// diagnostics: SDX_IGEMM_TRACE (main-loop timeline), SDX_IGEMM_ABLATE (IgemmParams::ablate)
 int igemm_trace_on() {
-  static const int v = [] {
-    const char* e = getenv("SDX_IGEMM_TRACE");
-    return e ? atoi(e) : 0;
-  }();
+  static const int v = (int)sdx_plan::env_int("SDX_IGEMM_TRACE", 0);
   return v;
 }
-
 int igemm_ablate() {
-  static const int a = [] {
-    const char* e = getenv("SDX_IGEMM_ABLATE");
-    return e ? atoi(e) : 0;
-  }();
+  static const int a = (int)sdx_plan::env_int("SDX_IGEMM_ABLATE", 0);
   return a;
 }
-
-int igemm_worder() {
-  static const int v = [] {
-    const char* e = getenv("SDX_WGRAD_ORDER");
-    return e ? atoi(e) : 1;
-  }();
-  return v;
-}
-
-int igemm_one() {
-  static const int v = [] {
-    const char* e = getenv("SDX_IGEMM_ONE");
-    return e ? atoi(e) : 1;
-  }();
-  return v;
-}
-// longest reduction (GEMM K) run on the single-stage DEPTH 3 form: forward
-// SDX_IGEMM_ONE_K (default 256), data gradient SDX_IGEMM_ONE_K_DGRAD (default BK = one
-// K-tile, the only case before round 6). Up to 256 the forward 1x1 GEMMs gain 5-12 % (3
-// blocks per CU instead of 2: l3.x.c3 32.1 -> 29.6 us, l2.x.c3 47.2 -> 42.3, stem 34.2 ->
-// 28.7); the dgrads are mixed (l1.0.c3 61.9 -> 56.4, l3.0.c1 65.0 -> 71.3), and K = 512
-// loses on both (profiles/one_stage_r6.txt)
-std::atomic<int>& igemm_one_k_ref(int mode) {
-  static std::atomic<int> f{[] {
-    const char* e = getenv("SDX_IGEMM_ONE_K");
-    return e ? atoi(e) : 256;
-  }()};
-  static std::atomic<int> d{[] {
-    const char* e = getenv("SDX_IGEMM_ONE_K_DGRAD");
-    return e ? atoi(e) : BK;
-  }()};
-  return mode == MODE_FWD ? f : d;
-}
-int igemm_one_k(int mode) { return igemm_one_k_ref(mode).load(std::memory_order_relaxed); }
 
 template <int MODE, int BM, int BN, int WM, int WN, int DEPTH, int VAR>
 hipError_t launch_v(bool one, int grid, const IgemmParams& p, hipStream_t s) {
@@ -1729,7 +1667,7 @@ hipError_t launch_k(bool bs, int grid, const IgemmParams& p, hipStream_t s) {
   // LDS-DMA main loops (DEPTH 3: two buffers; 6: in-wave pipelined ring; 7 / 8: tap reuse)
   // carry every epilogue variant; the single-stage (ONE) form is DEPTH 3 at one K-tile
   constexpr bool GLK = (DEPTH == 3 || DEPTH >= 6) && MODE != MODE_WGRAD;
-  const bool one = DEPTH == 3 && p.Kdim <= igemm_one_k(MODE) && igemm_one();
+  const bool one = sdx_plan::igemm_one_stage(MODE, DEPTH, p.Kdim, sdx_plan::knobs());
   if (MODE == MODE_FWD && p.bn_sc != nullptr) {
     // block-output BN-apply epilogue (forward-folded BN3): LDS-DMA tiles only
     if constexpr (MODE == MODE_FWD && GLK) return launch_v<MODE, BM, BN, WM, WN, DEPTH, 2>(one, grid, p, s);
@@ -1747,14 +1685,15 @@ hipError_t launch_k(bool bs, int grid, const IgemmParams& p, hipStream_t s) {
 }
 
 // WGRAD launch of variant VAR (bit 0: 1x1 fast path, bit 1: BN prologue) at the depth
-// launch_cfg picks for WGRAD
+// sdx_plan::igemm_loop picks for WGRAD
 template <int BM, int BN, int WM, int WN, int VAR>
 hipError_t launch_w(int grid, const IgemmParams& p, hipStream_t s) {
   const dim3 g(grid), b(64 * WM * WN);
   constexpr bool kDepth2 = BM == 64 && BN == 64;
-  if (VAR < 2 && igemm_glds() == 2)
+  const int depth = sdx_plan::igemm_loop(MODE_WGRAD, BM, BN, WM * WN, p.Kdim, 0, 0, VAR >= 2, false, sdx_plan::knobs());
+  if (VAR < 2 && depth == 3)
     hipLaunchKernelGGL((igemm_kernel<MODE_WGRAD, BM, BN, WM, WN, 3, VAR, false>), g, b, 0, s, p);
-  else if (kDepth2 && igemm_depth() == 2)
+  else if (kDepth2 && depth == 2)
     hipLaunchKernelGGL((igemm_kernel<MODE_WGRAD, BM, BN, WM, WN, kDepth2 ? 2 : 1, VAR, false>), g, b, 0, s, p);
   else
     hipLaunchKernelGGL((igemm_kernel<MODE_WGRAD, BM, BN, WM, WN, 1, VAR, false>), g, b, 0, s, p);
@@ -1791,27 +1730,21 @@ hipError_t launch_cfg(IgemmParams p, hipStream_t s) {
     if (k1) return launch_w<BM, BN, WM, WN, 1>(grid, p, s);
     return launch_w<BM, BN, WM, WN, 0>(grid, p, s);
   } else {
-  // depth 2 only where the second register stage fits without spilling (checked with
-  // -Rpass-analysis=kernel-resource-usage)
+  // the main loop by sdx_plan::igemm_loop; only the depths a tile is built for are instantiated
   constexpr bool kDepth2 = (BM == 64 && BN == 64) || (MODE == MODE_FWD && BM != 256);
+  constexpr bool kW1 = WM * WN == 8 && BM * BN == 256 * 128;
   const bool bs = MODE == MODE_DGRAD && p.bs.slab != nullptr;
-  {
-    // 8-wave 256x128 / 128x256 tiles at more than two K-tiles whose channel dim (FWD C,
-    // DGRAD K) is a multiple of BK (branch-free K decode): the in-wave pipelined loop (DEPTH 6)
-    constexpr bool kW1 = WM * WN == 8 && BM * BN == 256 * 128;
-    const int cdim_h = MODE == MODE_FWD ? p.g.C : p.g.K + p.a2_ch;
-    const int taps_h = MODE == MODE_FWD ? p.g.R * p.g.S : p.nr * p.ns;
-    const bool w1 = kW1 && p.Kdim > 2 * BK && p.in_scale == nullptr && cdim_h % BK == 0 && taps_h <= 32;
-    if (p.in_scale == nullptr && igemm_glds() != 0) {
-      if constexpr (kW1) {
-        if (w1) return launch_k<MODE, BM, BN, WM, WN, 6>(bs, grid, p, s);
-      }
-      return launch_k<MODE, BM, BN, WM, WN, 3>(bs, grid, p, s);
-    }
+  const int cdim_h = MODE == MODE_FWD ? p.g.C : p.g.K + p.a2_ch;
+  const int taps_h = MODE == MODE_FWD ? p.g.R * p.g.S : p.nr * p.ns;
+  const int depth = sdx_plan::igemm_loop(MODE, BM, BN, WM * WN, p.Kdim, cdim_h, taps_h, p.in_scale != nullptr, bs,
+                                         sdx_plan::knobs());
+  if constexpr (kW1) {
+    if (depth == 6) return launch_k<MODE, BM, BN, WM, WN, 6>(bs, grid, p, s);
   }
+  if (depth == 3) return launch_k<MODE, BM, BN, WM, WN, 3>(bs, grid, p, s);
   if (p.a2 != nullptr) return hipErrorInvalidValue;   // K-concatenation: LDS-DMA loops only
   if constexpr (kDepth2) {
-    if (igemm_depth() == 2 && !bs) {
+    if (depth == 2) {
       hipLaunchKernelGGL((igemm_kernel<MODE, BM, BN, WM, WN, 2, 0, false>), dim3(grid), dim3(64 * WM * WN), 0, s, p);
       SDX_LAUNCH_CHECK();
       return hipSuccess;
@@ -1821,78 +1754,26 @@ hipError_t launch_cfg(IgemmParams p, hipStream_t s) {
   }
 }
 
-// Geometry of the tap-reuse loop (DEPTH 7 / 8) for a BM-row tile; false = not supported:
-// a pad-1 3x3 stride-1 conv (DGRAD: the stride-1 class) whose tile rows are whole image
-// rows of whole images or of one image band, a channel dim of 64-channel chunks and a window
-// that fits the halo buffer. Swizzle phase t_ky: fragments of 16 output pixels span 1 row
-// (W >= 16), 2 rows (W = 8: ky = 0) or 4 rows (W = 4: ky = 4) — conflict-free ds_read_b128
-// lane groups for every tap (checked by brute force over the lane groups of the LDS table in
-// MI355X_MICROARCH.md); other widths are correct, not conflict-free.
-// SDX_TAP_PAD=0: no padded-row tiles (widths that do not divide BM stay on the implicit GEMM)
-bool tap_pad_enabled() {
-  static const bool on = [] {
-    const char* e = getenv("SDX_TAP_PAD");
-    return e == nullptr || atoi(e) != 0;
-  }();
-  return on;
-}
-
-bool tap_geom(IgemmParams& p, int bm, int depth, int mode) {
-  const ConvGeom& g = p.g;
-  if (g.R != 3 || g.S != 3 || g.stride != 1 || g.pad != 1 || g.P != g.H || g.Q != g.W) return false;
-  if (mode == MODE_DGRAD && (p.ncls > 1 || p.ph != 0 || p.pw != 0 || p.nr != 3 || p.ns != 3)) return false;
-  const int cdim = mode == MODE_FWD ? g.C : g.K;
-  const int HW = g.H * g.W;
-  if (cdim % 64 != 0) return false;
-  p.t_rw = 0;
-  int rw = g.W;
-  if (bm % g.W != 0 || !(HW % bm == 0 || bm % HW == 0)) {
-    // padded rows: a band of bm / rw whole image rows of rw = pow2 >= W virtual pixels each
-    // (fragments of 16 virtual pixels stay inside one row: rw >= 16). Single-chunk DEPTH-8
-    // tiles only: 56x56x64 fwd / dgrad 376 / 378 us vs 389 / 427 on the best implicit-GEMM
-    // tile, but the 128-row DEPTH-7 tile at 28x28x128 runs 446 / 419 vs 258 / 266
-    // (profiles/tap_pad_r6.txt, 1024 views)
-    rw = 16;
-    while (rw < g.W) rw <<= 1;
-    if (!tap_pad_enabled() || depth != 8 || bm % rw != 0 || g.H % (bm / rw) != 0) return false;
-    p.t_rw = rw;
-  }
-  p.t_rs = g.W + 2;
-  p.t_imgs = (p.t_rw == 0 && bm >= HW) ? bm / HW : 0;
-  const int rows = p.t_imgs > 0 ? g.H : bm / rw;
-  p.t_is = (rows + 2) * p.t_rs;
-  p.t_hp = (p.t_imgs > 0 ? p.t_imgs : 1) * p.t_is;
-  p.t_nhp = (p.t_hp + 7) / 8;
-  p.t_ky = g.W == 4 ? 4 : 0;
-  p.t_nch = cdim / 64;
-  if (p.t_nhp > tap_halo_kb(bm)) return false;
-  // padded rows: the last row's padded fragments read up to pixel (rows + 1)·t_rs + rw + 1,
-  // still inside the halo buffer
-  if (p.t_rw > 0 && (rows + 1) * p.t_rs + rw + 2 > tap_halo_kb(bm) * 8) return false;
-  if (bm == 256 && p.t_ky != 0) return false;   // the BM = 256 loop keeps 3 address variants
-  if (depth == 8 && p.t_nch != 1) return false;
-  return true;
-}
-
 template <int MODE, int BM, int BN, int WM, int WN, int DEPTH>
 hipError_t launch_tap(IgemmParams p, hipStream_t s) {
-  if (!tap_geom(p, BM, DEPTH, MODE)) return hipErrorInvalidValue;
+  sdx_plan::TapGeom t;
+  const int cdim = MODE == MODE_FWD ? p.g.C : p.g.K;
+  if (MODE == MODE_DGRAD && p.ncls > 1) return hipErrorInvalidValue;
+  if (!sdx_plan::tap_geom(p.g, cdim, BM, DEPTH, sdx_plan::knobs(), &t)) return hipErrorInvalidValue;
+  p.t_rw = t.t_rw; p.t_rs = t.t_rs; p.t_imgs = t.t_imgs; p.t_is = t.t_is;
+  p.t_hp = t.t_hp; p.t_nhp = t.t_nhp; p.t_ky = t.t_ky; p.t_nch = t.t_nch;
   // the in-kernel statistics reduction and the BN+ReLU operand prologue are not built here
   if (p.in_scale != nullptr) return hipErrorInvalidValue;
   p.ablate = igemm_ablate();
   p.trace = igemm_trace_on();
   // (padded rows: the virtual rows tile exactly — H is a multiple of the band height)
-  p.m_tiles = p.t_rw > 0 ? p.g.N * p.g.H * p.t_rw / BM : (p.M + BM - 1) / BM;
+  p.m_tiles = t.t_rw > 0 ? p.g.N * p.g.H * t.t_rw / BM : (p.M + BM - 1) / BM;
   p.n_tiles = (p.Ncol + BN - 1) / BN;
   const bool bs = MODE == MODE_DGRAD && p.bs.slab != nullptr;
   return launch_k<MODE, BM, BN, WM, WN, DEPTH>(bs, p.m_tiles * p.n_tiles, p, s);
 }
 
-// tile configs: 0 128x128 (2x2 waves of 64x64), 1 256x64 (4x1), 2 64x256 (1x4), 3 64x64 (2x2 waves of 32x32),
-// 4 128x128 with 8 waves (2x4 of 64x32: twice the waves per SIMD for latency hiding),
-// 5 256x128 with 8 waves (4x2 of 64x64, one block per CU), 6 128x256 with 8 waves (2x4 of
-// 64x64); both run the in-wave pipelined loop (DEPTH 6, 144 KiB LDS ring) at K > 128.
-// (7 / 8, 4-wave 64x128 wave tiles, measured slower than 5 / 6 in round 4 and removed.)
+// tile configs: the table at sdx_plan::tile_m (conv_plan.h)
 template <int MODE>
 hipError_t launch_any(IgemmParams p, int cfg, hipStream_t s) {
   switch (cfg) {
@@ -1903,9 +1784,7 @@ hipError_t launch_any(IgemmParams p, int cfg, hipStream_t s) {
     case 4: return launch_cfg<MODE, 128, 128, 2, 4>(p, s);
     case 5: return launch_cfg<MODE, 256, 128, 4, 2>(p, s);
     case 6: return launch_cfg<MODE, 128, 256, 2, 4>(p, s);
-    // tap-reuse 3x3 (FWD / stride-1 DGRAD only): 11 256x64 with 4 waves of 64x64 and one halo
-    // buffer (C = 64: two blocks per CU), 12 256x128 with 8 waves (4x2 of 64x64), 13 128x128
-    // with 8 waves (2x4 of 64x32)
+    // tap-reuse 3x3 (FWD / stride-1 DGRAD only)
     case 11:
       if constexpr (MODE != MODE_WGRAD) return launch_tap<MODE, 256, 64, 4, 1, 8>(p, s);
       return hipErrorInvalidValue;
@@ -1920,43 +1799,6 @@ hipError_t launch_any(IgemmParams p, int cfg, hipStream_t s) {
 }
 
 }  // namespace
-
-int igemm_tile_m(int cfg) {
-  static const int m[14] = {128, 256, 64, 64, 128, 256, 128, 0, 0, 0, 0, 256, 256, 128};
-  return (cfg >= 0 && cfg < 14) ? m[cfg] : 0;
-}
-int igemm_tile_n(int cfg) {
-  static const int n[14] = {128, 64, 256, 64, 128, 128, 256, 0, 0, 0, 0, 64, 128, 128};
-  return (cfg >= 0 && cfg < 14) ? n[cfg] : 0;
-}
-
-// tap-reuse tile config for a conv (FWD, or the stride-1 DGRAD with cdim = K, ncol = C), or -1
-int igemm_tap_cfg(const ConvGeom& g, int cdim, int ncol) {
-  if (g.R != 3 || g.S != 3 || g.stride != 1 || g.pad != 1 || cdim % 64 != 0) return -1;
-  const int cands[3] = {cdim == 64 && ncol <= 64 ? 11 : -1, g.W >= 8 ? 12 : -1, 13};
-  for (int cfg : cands) {
-    if (cfg < 0) continue;
-    IgemmParams p{};
-    p.g = g;
-    p.g.C = cdim;   // checked as a FWD geometry whose reduction channels are cdim
-    if (tap_geom(p, igemm_tile_m(cfg), cfg == 11 ? 8 : 7, MODE_FWD)) return cfg;
-  }
-  return -1;
-}
-
-// M-tiles (statistics-slab rows) of a stride-1 fwd / dgrad conv of M output rows under cfg: a
-// padded-row tap tile counts its virtual rows
-int64_t igemm_conv_mtiles(const ConvGeom& g, int cdim, int cfg, int64_t M) {
-  const int bm = igemm_tile_m(cfg);
-  if (bm <= 0) return 0;
-  if (cfg >= 11 && cfg <= 13) {
-    IgemmParams p{};
-    p.g = g;
-    p.g.C = cdim;
-    if (tap_geom(p, bm, cfg == 11 ? 8 : 7, MODE_FWD) && p.t_rw > 0) return (int64_t)g.N * g.H * p.t_rw / bm;
-  }
-  return (M + bm - 1) / bm;
-}
 
 namespace {
 void set_epi(IgemmParams& p, const GemmEpi* epi) {
@@ -2008,33 +1850,6 @@ hipError_t launch_conv_fwd(const ConvGeom& g, const void* x, const void* w, void
   return launch_any<MODE_FWD>(p, cfg, s);
 }
 
-void conv_dgrad_class(const ConvGeom& g, int ph, int pw, int* r0, int* nr, int* s0, int* ns, int* Hc, int* Wc) {
-  const int st = g.stride;
-  *r0 = (ph + g.pad) % st;
-  *s0 = (pw + g.pad) % st;
-  *nr = *r0 < g.R ? (g.R - *r0 + st - 1) / st : 0;
-  *ns = *s0 < g.S ? (g.S - *s0 + st - 1) / st : 0;
-  *Hc = ph < g.H ? (g.H - ph + st - 1) / st : 0;
-  *Wc = pw < g.W ? (g.W - pw + st - 1) / st : 0;
-}
-
-int conv_dgrad_class_mtiles(const ConvGeom& g, int ph, int pw, int cfg) {
-  int r0, nr, s0, ns, Hc, Wc;
-  conv_dgrad_class(g, ph, pw, &r0, &nr, &s0, &ns, &Hc, &Wc);
-  const int M = g.N * Hc * Wc, bm = igemm_tile_m(cfg);
-  if (g.stride == 1) return (int)igemm_conv_mtiles(g, g.K, cfg, M);   // (a tap tile may pad rows)
-  return (M + bm - 1) / bm;
-}
-
-// K-concatenated dgrad [dy | a2]·[Wd ; Mx] (BN3 fold): a stride-1 unpadded 1x1 whose dy
-// width is a power-of-two multiple of a2's (both multiples of BK), on the LDS-DMA loops
-bool conv_dgrad_cat_supported(const ConvGeom& g, int cat_ch) {
-  if (cat_ch <= 0 || g.R != 1 || g.S != 1 || g.stride != 1 || g.pad != 0 || g.P != g.H || g.Q != g.W) return false;
-  if (g.K % BK != 0 || cat_ch % BK != 0 || g.K % cat_ch != 0) return false;
-  const unsigned r = (unsigned)(g.K / cat_ch);
-  return (r & (r - 1)) == 0 && igemm_glds() != 0;
-}
-
 hipError_t launch_conv_dgrad_class(const ConvGeom& g, int ph, int pw, const void* dy, const void* wt, void* dx,
                                    const void* addend, int cfg, hipStream_t s, const void* addend_mask,
                                    const BnBwdStat* bstat, int addend_sub, const GemmEpi* epi) {
@@ -2052,14 +1867,15 @@ hipError_t launch_conv_dgrad_class(const ConvGeom& g, int ph, int pw, const void
   p.addend = (const uint16_t*)addend;
   p.ph = ph;
   p.pw = pw;
-  conv_dgrad_class(g, ph, pw, &p.r0, &p.nr, &p.s0, &p.ns, &p.Hc, &p.Wc);
-  p.M = g.N * p.Hc * p.Wc;
+  const sdx_plan::DgradClass c = sdx_plan::dgrad_class(g, ph, pw);
+  p.r0 = c.r0; p.nr = c.nr; p.s0 = c.s0; p.ns = c.ns; p.Hc = c.Hc; p.Wc = c.Wc;
+  p.M = c.M;
   if (p.M == 0) return hipSuccess;
   p.Ncol = g.C;
   p.Kdim = p.nr * p.ns * g.K;
   p.b_row = g.R * g.S * g.K;
   if (p.a2 != nullptr || p.a2_ch != 0) {
-    if (p.a2 == nullptr || !conv_dgrad_cat_supported(g, p.a2_ch)) return hipErrorInvalidValue;
+    if (p.a2 == nullptr || !sdx_plan::dgrad_cat_supported(g, p.a2_ch, sdx_plan::knobs())) return hipErrorInvalidValue;
     p.a2_sh = __builtin_ctz((unsigned)(g.K / p.a2_ch));
     p.a2_elems = (long)g.N * g.P * g.Q * p.a2_ch;
     p.Kdim += p.a2_ch;
@@ -2075,11 +1891,12 @@ hipError_t launch_conv_dgrad_class(const ConvGeom& g, int ph, int pw, const void
   return launch_any<MODE_DGRAD>(p, cfg, s);
 }
 
-hipError_t launch_conv_dgrad_merged(const ConvGeom& g, const void* dy, const void* wt, void* dx, const void* addend,
-                                    int cfg, hipStream_t s, const void* addend_mask, const BnBwdStat* bstat,
-                                    int addend_sub) {
+hipError_t launch_conv_dgrad_merged(const ConvGeom& g, const sdx_plan::DgradPlan& plan, const void* dy, const void* wt,
+                                    void* dx, const void* addend, hipStream_t s, const void* addend_mask,
+                                    const BnBwdStat* bstat, int addend_sub) {
   const int st = g.stride;
-  if (st < 2 || st * st > 4) return hipErrorInvalidValue;
+  if (!plan.merged || !plan.ok || st != 2) return hipErrorInvalidValue;
+  if (plan.ncls == 0) return hipSuccess;
   IgemmParams p{};
   p.addend_sub = addend_sub;
   if (bstat != nullptr) p.bs = *bstat;
@@ -2095,56 +1912,31 @@ hipError_t launch_conv_dgrad_merged(const ConvGeom& g, const void* dy, const voi
   p.b_ts = st * g.K;
   p.a_elems = (long)g.N * g.P * g.Q * g.K;
   p.b_elems = (long)p.Ncol * p.b_row;
-  // classes with more taps first (longest blocks dispatched first)
-  int order[4], n = 0;
-  for (int ph = 0; ph < st; ++ph)
-    for (int pw = 0; pw < st; ++pw) order[n++] = ph * st + pw;
-  auto taps = [&](int id) {
-    int r0, nr, s0, ns, Hc, Wc;
-    conv_dgrad_class(g, id / st, id % st, &r0, &nr, &s0, &ns, &Hc, &Wc);
-    return nr * ns;
-  };
-  for (int i = 1; i < n; ++i)
-    for (int j = i; j > 0 && taps(order[j]) > taps(order[j - 1]); --j) std::swap(order[j], order[j - 1]);
-  int maxk = 0, maxm = 0, maxt = 0, nc = 0;
-  for (int i = 0; i < n; ++i) {
-    IgemmParams::Cls& cd = p.cls[nc];
-    cd.ph = order[i] / st;
-    cd.pw = order[i] % st;
-    conv_dgrad_class(g, cd.ph, cd.pw, &cd.r0, &cd.nr, &cd.s0, &cd.ns, &cd.Hc, &cd.Wc);
-    cd.M = g.N * cd.Hc * cd.Wc;
-    if (cd.M == 0) continue;
-    cd.Kdim = cd.nr * cd.ns * g.K;
-    cd.b_t0 = (cd.r0 * g.S + cd.s0) * g.K;
-    maxk = cd.Kdim > maxk ? cd.Kdim : maxk;
-    maxm = cd.M > maxm ? cd.M : maxm;
-    maxt = cd.nr * cd.ns > maxt ? cd.nr * cd.ns : maxt;
-    ++nc;
+  // the plan's classes: those with more taps first (longest blocks dispatched first)
+  for (int i = 0; i < plan.ncls; ++i) {
+    const sdx_plan::DgradClass& c = plan.cls[i];
+    IgemmParams::Cls& cd = p.cls[i];
+    cd.ph = c.ph; cd.pw = c.pw; cd.Hc = c.Hc; cd.Wc = c.Wc;
+    cd.r0 = c.r0; cd.nr = c.nr; cd.s0 = c.s0; cd.ns = c.ns;
+    cd.M = c.M;
+    cd.Kdim = c.nr * c.ns * g.K;
+    cd.b_t0 = (c.r0 * g.S + c.s0) * g.K;
   }
-  if (nc == 0) return hipSuccess;
-  p.ncls = nc;
+  p.ncls = plan.ncls;
   // launch-level choices (main loop, single-stage form) see the largest class; the per-class
   // fields below are the first class's (every block overwrites them with its own)
   const IgemmParams::Cls& c0 = p.cls[0];
   p.ph = c0.ph; p.pw = c0.pw; p.Hc = c0.Hc; p.Wc = c0.Wc; p.r0 = c0.r0; p.s0 = c0.s0;
   p.nr = c0.nr; p.ns = c0.ns; p.b_t0 = c0.b_t0;
-  p.M = maxm;
-  p.Kdim = maxk;
-  (void)maxt;
-  return launch_any<MODE_DGRAD>(p, cfg, s);
+  p.M = plan.max_M;
+  p.Kdim = plan.max_Kdim;
+  return launch_any<MODE_DGRAD>(p, plan.cfg, s);
 }
 
-int conv_wgrad_splits(const ConvGeom& g, int cfg, int splits) {
-  const int Kd = g.N * g.P * g.Q;
-  if (splits < 1) splits = 1;
-  int per = (Kd + splits - 1) / splits;
-  per = ((per + BK - 1) / BK) * BK;
-  return (Kd + per - 1) / per;
-}
-
-hipError_t launch_conv_wgrad(const ConvGeom& g, const void* dy, const void* x, float* partial, float* dw, int cfg,
-                             int splits, int accumulate, hipStream_t s, const float* in_scale,
+hipError_t launch_conv_wgrad(const ConvGeom& g, const sdx_plan::WgradPlan& plan, const void* dy, const void* x,
+                             float* partial, float* dw, int accumulate, hipStream_t s, const float* in_scale,
                              const float* in_shift) {
+  if (!plan.ok || plan.family != sdx_plan::WGRAD_GENERIC) return hipErrorInvalidValue;
   IgemmParams p{};
   p.in_scale = in_scale;
   p.in_shift = in_shift;
@@ -2156,11 +1948,8 @@ hipError_t launch_conv_wgrad(const ConvGeom& g, const void* dy, const void* x, f
   p.Kdim = g.N * g.P * g.Q;
   p.a_elems = (long)g.N * g.P * g.Q * g.K;
   p.b_elems = (long)g.N * g.H * g.W * g.C;
-  if (splits < 1) splits = 1;
-  int per = (p.Kdim + splits - 1) / splits;
-  per = ((per + BK - 1) / BK) * BK;
-  p.k_per_split = per;
-  p.splits = (p.Kdim + per - 1) / per;
+  p.k_per_split = plan.per;
+  p.splits = plan.splits;
   p.div_pq = make_fastdiv((unsigned)(g.P * g.Q));
   p.div_q = make_fastdiv((unsigned)g.Q);
   auto log2_exact = [](int v) {
@@ -2168,14 +1957,17 @@ hipError_t launch_conv_wgrad(const ConvGeom& g, const void* dy, const void* x, f
     while ((1 << l) < v) ++l;
     return (1 << l) == v ? l : -1;
   };
-  p.worder = igemm_worder();
+  // WGRAD block order: 1 split-major (default), 0 tile-major
+  static const int worder = (int)sdx_plan::env_int("SDX_WGRAD_ORDER", 1);
+  p.worder = worder;
   p.lq = log2_exact(g.Q);
   p.lpq = log2_exact(g.P * g.Q);
   if (p.lq < 0 || p.lpq < 0) p.lq = p.lpq = -1;
   // a single split writes straight into dW (unless accumulating)
-  const bool direct = p.splits == 1 && !accumulate;
+  const bool direct = plan.direct && !accumulate;
+  if (!direct && partial == nullptr) return hipErrorInvalidValue;
   p.out = direct ? (void*)dw : (void*)partial;
-  hipError_t e = launch_any<MODE_WGRAD>(p, cfg, s);
+  hipError_t e = launch_any<MODE_WGRAD>(p, plan.cfg, s);
   if (e != hipSuccess || direct) return e;
   return launch_splitk_reduce(partial, p.splits, (long)p.M * p.Ncol / 4, dw, accumulate, s);
 }
@@ -2292,9 +2084,6 @@ hipError_t launch_splitk_reduce(const float* partial, int splits, long n4, float
   return hipSuccess;
 }
 
-// the BN-apply epilogue runs on the LDS-DMA tiles, not the register-staged ones
-bool conv_fwd_bnapply_supported() { return igemm_glds() != 0; }
-
 // the diagnostic timeline of the last traced launch (SDX_IGEMM_TRACE=1): 2 x kTraceSlots u64
 int igemm_trace_slots() { return kTraceSlots; }
 hipError_t igemm_trace_copy(unsigned long long* host, hipStream_t s) {
@@ -2304,6 +2093,3 @@ hipError_t igemm_trace_copy(unsigned long long* host, hipStream_t s) {
                              hipMemcpyDeviceToHost);
 }
 
-// single-stage reduction limits at run time (tests, A/B): mode 0 forward, 1 data gradient;
-// returns the previous limit
-int igemm_one_k_set(int mode, int k) { return igemm_one_k_ref(mode == 0 ? MODE_FWD : MODE_DGRAD).exchange(k); }

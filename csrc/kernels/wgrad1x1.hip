@@ -509,6 +509,7 @@ __global__ __launch_bounds__(W1_NT, 1) void wgrad1x1_pipe_kernel(W1Params p) {
 // Steps past the split's end DMA the zero page into their (never read) slot, keeping the
 // per-iteration DMA count uniform.
 constexpr int W1B_BM = 256;
+static_assert(W1_BM == sdx_plan::kW1Bm && W1B_BM == sdx_plan::kW1BigBm, "conv_plan.h plans these tiles");
 constexpr int W1B_NS = 4;   // LDS slots
 
 // One 16-B LDS-DMA per lane into LDS byte address lds_addr (wave-uniform) + 16·lane, as
@@ -672,130 +673,22 @@ __global__ __launch_bounds__(W1_NT, 1) void wgrad1x1_big_kernel(W1Params p) {
   }
 }
 
-// SDX_W1_BN=128 forces the 128-column tile on every shape (co-residency experiments: the
-// non-pipelined 128x128 kernel holds 112 VGPRs, so an 8-wave main-stream block fits beside it)
-// pixel-pair view (stride 1, a 64-channel side: the layer-1 bottleneck 1x1 convs, reference
-// networks/resnet_big.py:44,48 at planes = 64): two consecutive pixels' 64 channels form one
-// 128-wide row, so the kernel's 128-row / 128-column tiles stay whole. The GEMM over the
-// pair view also forms the even x odd cross blocks (MFMA work thrown away: these GEMMs are
-// HBM-bound), while dy and x are read at full 16-B chunks in one pass
-//
-// Opt-in (SDX_W1_PAIRS=1, or wgrad1x1_pairs_set): measured no faster than the generic
-// kernel at CIFAR (65-68 vs 70 us stand-alone at 256 blocks, in-step within noise) and slower
-// at config 5 (71.3 vs 70.5 ms/step): the 32-pixel-pair step loop is latency-bound once its
-// MFMA work doubles (profiles/wgrad1x1_pairs_r5.txt)
-std::atomic<int>& w1_pairs_flag() {
-  static std::atomic<int> on{[] {
-    const char* e = getenv("SDX_W1_PAIRS");
-    return e != nullptr && atoi(e) != 0 ? 1 : 0;
-  }()};
-  return on;
-}
-bool w1_pairs(const ConvGeom& g) {
-  return w1_pairs_flag().load(std::memory_order_relaxed) != 0 && g.stride == 1 && g.R == 1 && g.S == 1 && g.pad == 0 && (g.K == 64 || g.C == 64) && g.K % 64 == 0 &&
-         g.C % 64 == 0 && ((long)g.N * g.P * g.Q) % 64 == 0;
-}
-int w1_kv(const ConvGeom& g) { return w1_pairs(g) ? 2 * g.K : g.K; }
-int w1_cv(const ConvGeom& g) { return w1_pairs(g) ? 2 * g.C : g.C; }
-
-// the 256-row LDS-DMA kernel: dy channels % 256, the non-GEN x addressing (stride 1, or a
-// strided shortcut whose 32-pixel step is whole output rows), not the pixel-pair view.
-// SDX_W1_BIG=0: the 128-row kernels for every shape
-bool w1_pipe_enabled(const ConvGeom& g);
-std::atomic<int>& w1_big_flag() {
-  static std::atomic<int> on{[] {
-    const char* e = getenv("SDX_W1_BIG");
-    return e == nullptr ? 1 : atoi(e) < 0 ? 0 : atoi(e) > 2 ? 2 : atoi(e);
-  }()};
-  return on;
-}
-// SDX_W1_BIG / wgrad1x1_big_set: 0 off, 1 (default) by the rule below, 2 every eligible shape.
-// Only for GEMMs with steps_total x tiles >= SDX_W1_BIG_MIN (default 8192: >= 64 steps per
-// split at the 128-block in-step target). Stand-alone the kernel is 2-12 % faster on every
-// layer 2-4 shape; in the step, on every shape, it made the step 0.04 ms SLOWER (11.786 vs
-// 11.749 ms, 3 interleaved rounds, profiles/w1_big_ab_r6.txt): its 128 KiB of LDS per block
-// leaves no room for a main-stream block on its CU, and at 32 steps per split its fp32 slab
-// round trip (twice the old kernel's at the same block count) eats the gain. The long-split
-// shapes (projection blocks, l2 expand convs) keep 9-12 %.
-bool w1_big(const ConvGeom& g) {
-  static const long min_work = [] {
-    const char* e = getenv("SDX_W1_BIG_MIN");
-    return e ? atol(e) : 8192L;
-  }();
-  const int mode = w1_big_flag().load(std::memory_order_relaxed);   // 0 off, 1 by the rule, 2 always
-  if (!(mode != 0 && !w1_pairs(g) && g.K % W1B_BM == 0 && g.C % 128 == 0 &&
-        w1_pipe_enabled(g) && (g.stride == 1 || 32 % g.Q == 0)))
-    return false;
-  const long steps = (long)g.N * g.P * g.Q / 32;
-  const long tiles = (long)(g.K / W1B_BM) * (g.C / (g.C % 256 == 0 ? 256 : 128));
-  return mode == 2 || steps * tiles >= min_work;
-}
-
-int wgrad1x1_bn(const ConvGeom& g) {
-  static const int force = [] {
-    const char* e = getenv("SDX_W1_BN");
-    return e ? atoi(e) : 0;
-  }();
-  if (force == 128) return 128;
-  return w1_cv(g) % 256 == 0 ? 256 : 128;
-}
-
-bool w1_pipe_enabled(const ConvGeom& g) {
-  static const bool on = [] {
-    const char* e = getenv("SDX_W1_PIPE");
-    return e == nullptr || atoi(e) != 0;
-  }();
-  // 32-bit element offsets: dy (output pixels) and x (input pixels)
-  return on && (long)g.N * g.P * g.Q * g.K < (1L << 31) && (long)g.N * g.H * g.W * g.C < (1L << 31);
-}
-
 }  // namespace
 
-// stride 1 (any image size), or a strided 1x1 (projection shortcut, reference
-// networks/resnet_big.py:50-55) on the pipelined kernel when the input is exactly st x the
-// output (Q | 32: the x source of a step pixel is base + step·const; otherwise the GEN
-// instantiation divides the step pixel index by Q)
-bool wgrad1x1_supported(const ConvGeom& g) {
-  static const bool strided_on = [] {   // SDX_W1_STRIDED=0: strided shortcuts on the generic kernel
-    const char* e = getenv("SDX_W1_STRIDED");
-    return e == nullptr || atoi(e) != 0;
-  }();
-  const bool strided_ok = strided_on && g.stride > 1 && g.H == g.stride * g.P && g.W == g.stride * g.Q &&
-                          (long)g.N * g.P * g.Q * g.Q < (1L << 32) &&
-                          w1_pipe_enabled(g);
-  if (g.R == 1 && g.S == 1 && g.pad == 0 && g.stride == 1 && g.P == g.H && g.Q == g.W && w1_pairs(g))
-    return w1_pipe_enabled(g);
-  return g.R == 1 && g.S == 1 && g.pad == 0 && (g.stride == 1 ? (g.P == g.H && g.Q == g.W) : strided_ok) &&
-         g.K % W1_BM == 0 && g.C % 128 == 0 && ((long)g.N * g.P * g.Q) % 32 == 0;
-}
-
-int wgrad1x1_tiles(const ConvGeom& g) {
-  if (w1_big(g)) return (g.K / W1B_BM) * (g.C / wgrad1x1_bn(g));
-  return (w1_kv(g) / W1_BM) * (w1_cv(g) / wgrad1x1_bn(g));
-}
-
-int wgrad1x1_steps(const ConvGeom& g) { return (int)((long)g.N * g.P * g.Q / (w1_pairs(g) ? 64 : 32)); }
-
-int wgrad1x1_slices(const ConvGeom& g, int splits) { return w1_pairs(g) ? 2 * splits : splits; }
-
-bool wgrad1x1_pair_view(const ConvGeom& g) { return w1_pairs(g); }
-
-int wgrad1x1_pairs_set(int on) { return w1_pairs_flag().exchange(on ? 1 : 0); }
-
-int wgrad1x1_big_set(int mode) { return w1_big_flag().exchange(mode < 0 ? 0 : mode > 2 ? 2 : mode); }
-
-hipError_t launch_wgrad1x1(const ConvGeom& g, const void* dy, const void* x, float* partial, float* dw, int splits,
-                           int accumulate, hipStream_t s) {
-  if (!wgrad1x1_supported(g) || splits < 1) return hipErrorInvalidValue;
+// which kernel, tile and view a shape runs: sdx_plan::w1_geom (conv_plan.h)
+hipError_t launch_wgrad1x1(const ConvGeom& g, const sdx_plan::WgradPlan& plan, const void* dy, const void* x,
+                           float* partial, float* dw, int accumulate, hipStream_t s) {
+  if (!plan.ok || plan.family != sdx_plan::WGRAD_1X1) return hipErrorInvalidValue;
+  const sdx_plan::W1Geom& w = plan.w1;
   W1Params p{};
   p.dy = (const uint16_t*)dy;
   p.x = (const uint16_t*)x;
-  p.pairs = w1_pairs(g) ? 1 : 0;
+  p.pairs = w.pairs ? 1 : 0;
   p.K0 = g.K;
   p.C0 = g.C;
-  p.K = w1_kv(g);
-  p.C = w1_cv(g);
-  p.steps_total = wgrad1x1_steps(g);
+  p.K = w.Kv;
+  p.C = w.Cv;
+  p.steps_total = w.steps;
   if (g.stride == 1) {
     p.xst = 1, p.xq = 32, p.xw = 32;   // xpix(j) = j
     p.x_step = 32 * p.C;
@@ -804,35 +697,33 @@ hipError_t launch_wgrad1x1(const ConvGeom& g, const void* dy, const void* x, flo
     p.x_step = 32 % g.Q == 0 ? g.stride * g.W * (32 / g.Q) * g.C : 0;
     p.xmagic = (unsigned)((1ULL << 32) / (unsigned)g.Q + 1);
   }
-  p.steps_per_split = (p.steps_total + splits - 1) / splits;
-  p.splits = (p.steps_total + p.steps_per_split - 1) / p.steps_per_split;
-  const int bn = wgrad1x1_bn(g);
-  const bool big = w1_big(g);
-  p.k_tiles = p.K / (big ? W1B_BM : W1_BM);
-  p.c_tiles = p.C / bn;
-  const bool direct = p.splits == 1 && !accumulate && !p.pairs;
+  p.steps_per_split = plan.per;
+  p.splits = plan.splits;
+  const int bn = w.bn;
+  p.k_tiles = w.k_tiles;
+  p.c_tiles = w.c_tiles;
+  const bool direct = plan.direct && !accumulate;
   if (!direct && partial == nullptr) return hipErrorInvalidValue;
   p.part = direct ? dw : partial;
   const dim3 grid(p.k_tiles * p.c_tiles * p.splits), block(W1_NT);
-  if (big) {
-    if (bn == 256) hipLaunchKernelGGL(wgrad1x1_big_kernel<256>, grid, block, 0, s, p);
-    else hipLaunchKernelGGL(wgrad1x1_big_kernel<128>, grid, block, 0, s, p);
-  } else if (w1_pipe_enabled(g)) {   // (a strided shape is supported only when it is)
-    const bool gen = g.stride > 1 && 32 % g.Q != 0;
-    if (gen) {
+  switch (w.kind) {
+    case sdx_plan::W1_BIG:
+      if (bn == 256) hipLaunchKernelGGL(wgrad1x1_big_kernel<256>, grid, block, 0, s, p);
+      else hipLaunchKernelGGL(wgrad1x1_big_kernel<128>, grid, block, 0, s, p);
+      break;
+    case sdx_plan::W1_PIPE_GEN:
       if (bn == 256) hipLaunchKernelGGL((wgrad1x1_pipe_kernel<256, true>), grid, block, 0, s, p);
       else hipLaunchKernelGGL((wgrad1x1_pipe_kernel<128, true>), grid, block, 0, s, p);
-    } else if (bn == 256) {
-      hipLaunchKernelGGL((wgrad1x1_pipe_kernel<256, false>), grid, block, 0, s, p);
-    } else {
-      hipLaunchKernelGGL((wgrad1x1_pipe_kernel<128, false>), grid, block, 0, s, p);
-    }
-  } else if (bn == 256) {
-    hipLaunchKernelGGL(wgrad1x1_kernel<256>, grid, block, 0, s, p);
-  } else {
-    hipLaunchKernelGGL(wgrad1x1_kernel<128>, grid, block, 0, s, p);
+      break;
+    case sdx_plan::W1_PIPE:
+      if (bn == 256) hipLaunchKernelGGL((wgrad1x1_pipe_kernel<256, false>), grid, block, 0, s, p);
+      else hipLaunchKernelGGL((wgrad1x1_pipe_kernel<128, false>), grid, block, 0, s, p);
+      break;
+    default:
+      if (bn == 256) hipLaunchKernelGGL(wgrad1x1_kernel<256>, grid, block, 0, s, p);
+      else hipLaunchKernelGGL(wgrad1x1_kernel<128>, grid, block, 0, s, p);
   }
   SDX_LAUNCH_CHECK();
   if (direct) return hipSuccess;
-  return launch_splitk_reduce(partial, p.pairs ? 2 * p.splits : p.splits, (long)g.K * g.C / 4, dw, accumulate, s);
+  return launch_splitk_reduce(partial, (int)plan.slices, (long)g.K * g.C / 4, dw, accumulate, s);
 }

@@ -652,114 +652,61 @@ __global__ __launch_bounds__(W3_NT, 1) void wgrad3x3_pad_kernel(W3Params p) {
   }
 }
 
-// padded-slot kernel: slot width WS (next power of two >= W) for stride-1 widths that are not
-// one of {4, 8, 16, 32}
-int w3_pad_ws(const ConvGeom& g) {
-  static const bool on = [] {   // SDX_W3_PAD=0: those widths on the generic kernel
-    const char* e = getenv("SDX_W3_PAD");
-    return e == nullptr || atoi(e) != 0;
-  }();
-  if (!on || g.stride != 1 || g.W == 4 || g.W == 8 || g.W == 16 || g.W == 32 || g.W < 5 || g.W > 64) return 0;
-  const int ws = g.W <= 8 ? 8 : g.W <= 16 ? 16 : g.W <= 32 ? 32 : 64;
-  const int sw = ws < 32 ? ws : 32, spr = ws / sw, rps = 32 / sw;
-  return ((long)g.N * g.H * spr) % rps == 0 ? ws : 0;
-}
-
-// stride-2 slots per output row: Q itself (4/8/16/32), else the next of 8/16/32 above it
-// (0: unsupported); a step is 32/slots whole output rows
-int w3_s2_slots(const ConvGeom& g) {
-  if (g.Q == 4 || g.Q == 8 || g.Q == 16 || g.Q == 32) return g.Q;
-  // (w3_pad_ws of the output-sized stride-1 geometry: honours SDX_W3_PAD)
-  if (g.Q < 5 || g.Q > 32 || !w3_pad_ws(ConvGeom{g.N, g.P, g.Q, g.C, g.K, 3, 3, g.P, g.Q, 1, 1})) return 0;
-  const int sq = g.Q <= 8 ? 8 : g.Q <= 16 ? 16 : 32;
-  return ((long)g.N * g.P) % (32 / sq) == 0 ? sq : 0;
-}
-
 }  // namespace
 
-bool wgrad3x3_supported(const ConvGeom& g) {
-  static const bool s2_on = [] {   // SDX_W3_S2=0: stride-2 3x3 wgrads on the generic kernel
-    const char* e = getenv("SDX_W3_S2");
-    return e == nullptr || atoi(e) != 0;
-  }();
-  const bool q_ok = g.Q == 4 || g.Q == 8 || g.Q == 16 || g.Q == 32;
-  if (g.stride == 2 && s2_on && g.R == 3 && g.S == 3 && g.pad == 1 && g.P == g.Q && g.H == 2 * g.P &&
-      g.W == 2 * g.Q && g.C % 64 == 0 && g.K % 64 == 0 && !q_ok && w3_s2_slots(g) > 0)
-    return true;   // padded output rows
-  const bool geo = g.stride == 1 ? (g.P == g.H && g.Q == g.W)
-                                 : (s2_on && g.stride == 2 && g.H == 2 * g.P && g.W == 2 * g.Q);
-  const bool base = g.R == 3 && g.S == 3 && g.pad == 1 && g.P == g.Q && geo && g.C % 64 == 0 && g.K % 64 == 0;
-  if (base && g.stride == 1 && g.H == g.W && w3_pad_ws(g) > 0) return true;   // padded slots
-  return base && q_ok && ((long)g.N * g.P * g.Q) % 32 == 0;
-}
-
-int wgrad3x3_tiles(const ConvGeom& g) { return (g.K / 64) * (g.C / 64); }
-
-int wgrad3x3_steps(const ConvGeom& g) {
-  const int ws = (g.stride == 1 && g.H == g.W) ? w3_pad_ws(g) : 0;
-  if (ws > 0) {   // segments of the padded-slot kernel / segments per step
-    const int sw = ws < 32 ? ws : 32;
-    return (int)((long)g.N * g.H * (ws / sw) / (32 / sw));
-  }
-  if (g.stride == 2 && !(g.Q == 4 || g.Q == 8 || g.Q == 16 || g.Q == 32)) {   // padded rows
-    const int sq = w3_s2_slots(g);
-    return (int)((long)g.N * g.P / (32 / sq));
-  }
-  return (int)((long)g.N * g.P * g.Q / 32);
-}
-
-hipError_t launch_wgrad3x3(const ConvGeom& g, const void* dy, const void* x, float* partial, float* dw, int splits,
-                           int accumulate, hipStream_t s) {
-  if (!wgrad3x3_supported(g) || splits < 1) return hipErrorInvalidValue;
+// which kernel and slot width a shape runs: sdx_plan::w3_geom (conv_plan.h)
+hipError_t launch_wgrad3x3(const ConvGeom& g, const sdx_plan::WgradPlan& plan, const void* dy, const void* x,
+                           float* partial, float* dw, int accumulate, hipStream_t s) {
+  if (!plan.ok || plan.family != sdx_plan::WGRAD_3X3) return hipErrorInvalidValue;
   W3Params p{};
   p.dy = (const uint16_t*)dy;
   p.x = (const uint16_t*)x;
   p.K = g.K;
   p.C = g.C;
-  p.steps_total = wgrad3x3_steps(g);
-  p.steps_per_split = (p.steps_total + splits - 1) / splits;
-  p.splits = (p.steps_total + p.steps_per_split - 1) / p.steps_per_split;
+  p.steps_total = plan.w3.steps;
+  p.steps_per_split = plan.per;
+  p.splits = plan.splits;
   p.k_tiles = g.K / 64;
   p.c_tiles = g.C / 64;
   // one split straight into dW (unless accumulating into it)
-  const bool direct = p.splits == 1 && !accumulate;
+  const bool direct = plan.direct && !accumulate;
   if (!direct && partial == nullptr) return hipErrorInvalidValue;
   p.part = direct ? dw : partial;
   const dim3 grid(p.k_tiles * p.c_tiles * p.splits), block(W3_NT);
   p.h = g.H;
   p.w = g.W;
-  const int ws = (g.stride == 1 && g.H == g.W) ? w3_pad_ws(g) : 0;
-  if (ws > 0) {
-    switch (ws) {
-      case 8: hipLaunchKernelGGL(wgrad3x3_pad_kernel<8>, grid, block, 0, s, p); break;
-      case 16: hipLaunchKernelGGL(wgrad3x3_pad_kernel<16>, grid, block, 0, s, p); break;
-      case 32: hipLaunchKernelGGL(wgrad3x3_pad_kernel<32>, grid, block, 0, s, p); break;
-      default: hipLaunchKernelGGL(wgrad3x3_pad_kernel<64>, grid, block, 0, s, p); break;
-    }
-  } else if (g.stride == 2) {
-    const bool pad = !(g.Q == 4 || g.Q == 8 || g.Q == 16 || g.Q == 32);
-    const int sq = w3_s2_slots(g);
-    if (pad) {
-      switch (sq) {
+  const int slot = plan.w3.slot;
+  switch (plan.w3.kind) {
+    case sdx_plan::W3_PAD:
+      switch (slot) {
+        case 8: hipLaunchKernelGGL(wgrad3x3_pad_kernel<8>, grid, block, 0, s, p); break;
+        case 16: hipLaunchKernelGGL(wgrad3x3_pad_kernel<16>, grid, block, 0, s, p); break;
+        case 32: hipLaunchKernelGGL(wgrad3x3_pad_kernel<32>, grid, block, 0, s, p); break;
+        default: hipLaunchKernelGGL(wgrad3x3_pad_kernel<64>, grid, block, 0, s, p); break;
+      }
+      break;
+    case sdx_plan::W3_S2_PAD:
+      switch (slot) {
         case 8: hipLaunchKernelGGL((wgrad3x3_s2_kernel<8, true>), grid, block, 0, s, p); break;
         case 16: hipLaunchKernelGGL((wgrad3x3_s2_kernel<16, true>), grid, block, 0, s, p); break;
         default: hipLaunchKernelGGL((wgrad3x3_s2_kernel<32, true>), grid, block, 0, s, p); break;
       }
-    } else {
-      switch (g.Q) {
+      break;
+    case sdx_plan::W3_S2:
+      switch (slot) {
         case 4: hipLaunchKernelGGL((wgrad3x3_s2_kernel<4, false>), grid, block, 0, s, p); break;
         case 8: hipLaunchKernelGGL((wgrad3x3_s2_kernel<8, false>), grid, block, 0, s, p); break;
         case 16: hipLaunchKernelGGL((wgrad3x3_s2_kernel<16, false>), grid, block, 0, s, p); break;
         default: hipLaunchKernelGGL((wgrad3x3_s2_kernel<32, false>), grid, block, 0, s, p); break;
       }
-    }
-  } else {
-    switch (g.W) {
-      case 4: hipLaunchKernelGGL(wgrad3x3_kernel<4>, grid, block, 0, s, p); break;
-      case 8: hipLaunchKernelGGL(wgrad3x3_kernel<8>, grid, block, 0, s, p); break;
-      case 16: hipLaunchKernelGGL(wgrad3x3_kernel<16>, grid, block, 0, s, p); break;
-      default: hipLaunchKernelGGL(wgrad3x3_kernel<32>, grid, block, 0, s, p); break;
-    }
+      break;
+    default:
+      switch (slot) {
+        case 4: hipLaunchKernelGGL(wgrad3x3_kernel<4>, grid, block, 0, s, p); break;
+        case 8: hipLaunchKernelGGL(wgrad3x3_kernel<8>, grid, block, 0, s, p); break;
+        case 16: hipLaunchKernelGGL(wgrad3x3_kernel<16>, grid, block, 0, s, p); break;
+        default: hipLaunchKernelGGL(wgrad3x3_kernel<32>, grid, block, 0, s, p); break;
+      }
   }
   SDX_LAUNCH_CHECK();
   if (direct) return hipSuccess;
