@@ -1,18 +1,28 @@
 // Bindings for the GPU data-pipeline kernels (aug.hip).
 #include "ops_decl.h"
+#include "blur_plan.h"
 #include "launchers.h"
 
 namespace sdx_bind {
 namespace {
 
-// seed_t (optional int64 GPU scalar) overrides `seed` at kernel run time, so a captured
-// hipGraph draws fresh augmentations on every replay.
-torch::Tensor gpu_augment(torch::Tensor data, torch::Tensor idx, int64_t S, int64_t n_views, int64_t seed,
-                          std::vector<double> mean, std::vector<double> std, double scale_lo, double scale_hi,
-                          double ratio_lo, double ratio_hi, double jitter_p, double bright, double contrast,
-                          double sat, double hue, double gray_p, bool do_crop, bool do_flip,
-                          c10::optional<torch::Tensor> seed_t, c10::optional<torch::Tensor> offs,
-                          c10::optional<torch::Tensor> hw) {
+struct AugArgs {
+  bool ragged;
+  const int64_t* seed_dev;
+  int64_t B;
+  float mean[3], std[3];
+  int H, W;
+  long n_data;
+  const int64_t* offs;
+  const int32_t* hw;
+};
+
+// the argument checks both augmentation ops share
+AugArgs check_aug_args(const torch::Tensor& data, const torch::Tensor& idx, int64_t S, int64_t n_views,
+                       const std::vector<double>& mean, const std::vector<double>& std,
+                       const c10::optional<torch::Tensor>& seed_t, const c10::optional<torch::Tensor>& offs,
+                       const c10::optional<torch::Tensor>& hw) {
+  AugArgs a{};
   const bool ragged = offs.has_value();
   TORCH_CHECK(ragged == hw.has_value(), "offs and hw must be given together");
   if (ragged) {
@@ -32,26 +42,73 @@ torch::Tensor gpu_augment(torch::Tensor data, torch::Tensor idx, int64_t S, int6
               "idx must be a contiguous int64 GPU vector");
   TORCH_CHECK(mean.size() == 3 && std.size() == 3, "mean/std need 3 values");
   TORCH_CHECK(S >= 1 && n_views >= 1 && idx.size(0) >= 1, "bad sizes");
-  const int64_t* sd_dev = nullptr;
   if (seed_t.has_value()) {
     TORCH_CHECK(seed_t->is_cuda() && seed_t->scalar_type() == at::kLong && seed_t->numel() == 1,
                 "seed_t must be an int64 GPU scalar");
-    sd_dev = seed_t->data_ptr<int64_t>();
+    a.seed_dev = seed_t->data_ptr<int64_t>();
   }
+  a.ragged = ragged;
+  a.B = idx.size(0);
+  for (int k = 0; k < 3; ++k) { a.mean[k] = (float)mean[k]; a.std[k] = (float)std[k]; }
+  a.H = ragged ? 0 : (int)data.size(1);
+  a.W = ragged ? 0 : (int)data.size(2);
+  a.n_data = ragged ? (long)offs->size(0) : (long)data.size(0);
+  a.offs = ragged ? offs->data_ptr<int64_t>() : nullptr;
+  a.hw = ragged ? hw->data_ptr<int32_t>() : nullptr;
+  return a;
+}
+
+// seed_t (optional int64 GPU scalar) overrides `seed` at kernel run time, so a captured
+// hipGraph draws fresh augmentations on every replay.
+torch::Tensor gpu_augment(torch::Tensor data, torch::Tensor idx, int64_t S, int64_t n_views, int64_t seed,
+                          std::vector<double> mean, std::vector<double> std, double scale_lo, double scale_hi,
+                          double ratio_lo, double ratio_hi, double jitter_p, double bright, double contrast,
+                          double sat, double hue, double gray_p, bool do_crop, bool do_flip,
+                          c10::optional<torch::Tensor> seed_t, c10::optional<torch::Tensor> offs,
+                          c10::optional<torch::Tensor> hw) {
+  const AugArgs a = check_aug_args(data, idx, S, n_views, mean, std, seed_t, offs, hw);
   c10::DeviceGuard dg(data.device());
-  const int64_t B = idx.size(0);
-  auto out = torch::empty({n_views * B, S, S, 8}, data.options().dtype(at::kBFloat16));
-  float m[3], sd[3];
-  for (int k = 0; k < 3; ++k) { m[k] = (float)mean[k]; sd[k] = (float)std[k]; }
-  const int H = ragged ? 0 : (int)data.size(1), W = ragged ? 0 : (int)data.size(2);
-  const long n_data = ragged ? (long)offs->size(0) : (long)data.size(0);
-  check_hip(launch_gpu_augment(data.data_ptr<uint8_t>(), idx.data_ptr<int64_t>(), (int)B, H, W, (int)S, (int)n_views,
-                               (uint64_t)seed, m, sd, (float)scale_lo,
-                               (float)scale_hi, (float)ratio_lo, (float)ratio_hi, (float)jitter_p, (float)bright,
-                               (float)contrast, (float)sat, (float)hue, (float)gray_p, do_crop ? 1 : 0,
-                               do_flip ? 1 : 0, sd_dev, out.data_ptr(), cur_stream(), n_data,
-                               ragged ? offs->data_ptr<int64_t>() : nullptr, ragged ? hw->data_ptr<int32_t>() : nullptr),
+  auto out = torch::empty({n_views * a.B, S, S, 8}, data.options().dtype(at::kBFloat16));
+  check_hip(launch_gpu_augment(data.data_ptr<uint8_t>(), idx.data_ptr<int64_t>(), (int)a.B, a.H, a.W, (int)S,
+                               (int)n_views, (uint64_t)seed, a.mean, a.std, (float)scale_lo, (float)scale_hi,
+                               (float)ratio_lo, (float)ratio_hi, (float)jitter_p, (float)bright, (float)contrast,
+                               (float)sat, (float)hue, (float)gray_p, do_crop ? 1 : 0, do_flip ? 1 : 0, a.seed_dev,
+                               out.data_ptr(), cur_stream(), a.n_data, a.offs, a.hw),
             "gpu_augment");
+  return out;
+}
+
+// gpu_augment with the Gaussian-blur stage (aug.hip aug_blur_kernel). blur_kernel 0 = automatic
+// from S, rows 0 = automatic rows per barrier round (blur_plan.h); a request the plan cannot
+// serve is an error here, never another kernel.
+torch::Tensor gpu_augment_blur(torch::Tensor data, torch::Tensor idx, int64_t S, int64_t n_views, int64_t seed,
+                               std::vector<double> mean, std::vector<double> std, double scale_lo, double scale_hi,
+                               double ratio_lo, double ratio_hi, double jitter_p, double bright, double contrast,
+                               double sat, double hue, double gray_p, bool do_crop, bool do_flip, double blur_p,
+                               int64_t blur_kernel, double sigma_lo, double sigma_hi,
+                               c10::optional<torch::Tensor> seed_t, c10::optional<torch::Tensor> offs,
+                               c10::optional<torch::Tensor> hw, int64_t rows) {
+  const AugArgs a = check_aug_args(data, idx, S, n_views, mean, std, seed_t, offs, hw);
+  TORCH_CHECK(blur_p >= 0.0 && blur_p <= 1.0, "blur_p must be in [0, 1]");
+  TORCH_CHECK((float)sigma_lo > 0.f && (float)sigma_lo <= (float)sigma_hi, "blur sigma needs 0 < lo <= hi");
+  TORCH_CHECK(blur_kernel == 0 || (blur_kernel >= 3 && blur_kernel % 2 == 1), "blur kernel size must be odd and >= 3");
+  const int64_t k = blur_kernel > 0 ? blur_kernel : sdx_blur::auto_kernel(S);
+  TORCH_CHECK((k - 1) / 2 <= S - 1, "blur radius ", (k - 1) / 2, " exceeds size - 1 = ", S - 1,
+              ": reflect padding is undefined");
+  TORCH_CHECK(rows >= 0 && rows <= sdx_blur::kMaxRows, "rows per round must be in [0, ", sdx_blur::kMaxRows, "]");
+  sdx_blur::Plan pl{};
+  TORCH_CHECK(sdx_blur::make_plan(S, blur_kernel, rows, &pl), "blur of kernel size ", k, " at size ", S,
+              " does not fit the ", sdx_blur::kLdsPerCu / 1024, " KiB LDS");
+  c10::DeviceGuard dg(data.device());
+  auto out = torch::empty({n_views * a.B, S, S, 8}, data.options().dtype(at::kBFloat16));
+  check_hip(launch_gpu_augment_blur(data.data_ptr<uint8_t>(), idx.data_ptr<int64_t>(), (int)a.B, a.H, a.W, (int)S,
+                                    (int)n_views, (uint64_t)seed, a.mean, a.std, (float)scale_lo, (float)scale_hi,
+                                    (float)ratio_lo, (float)ratio_hi, (float)jitter_p, (float)bright,
+                                    (float)contrast, (float)sat, (float)hue, (float)gray_p, do_crop ? 1 : 0,
+                                    do_flip ? 1 : 0, (float)blur_p, (int)blur_kernel, (float)sigma_lo,
+                                    (float)sigma_hi, (int)rows, a.seed_dev, out.data_ptr(), cur_stream(), a.n_data,
+                                    a.offs, a.hw),
+            "gpu_augment_blur");
   return out;
 }
 
@@ -66,6 +123,16 @@ void register_data(pybind11::module& m) {
         pybind11::arg("gray_p"), pybind11::arg("do_crop"), pybind11::arg("do_flip"),
         pybind11::arg("seed_t") = pybind11::none(), pybind11::arg("offs") = pybind11::none(),
         pybind11::arg("hw") = pybind11::none());
+  m.def("gpu_augment_blur", &gpu_augment_blur,
+        "fused SimCLR augmentation with the Gaussian-blur stage -> NHWC bf16 (C padded to 8)",
+        pybind11::arg("data"), pybind11::arg("idx"), pybind11::arg("S"), pybind11::arg("n_views"),
+        pybind11::arg("seed"), pybind11::arg("mean"), pybind11::arg("std"), pybind11::arg("scale_lo"),
+        pybind11::arg("scale_hi"), pybind11::arg("ratio_lo"), pybind11::arg("ratio_hi"), pybind11::arg("jitter_p"),
+        pybind11::arg("bright"), pybind11::arg("contrast"), pybind11::arg("sat"), pybind11::arg("hue"),
+        pybind11::arg("gray_p"), pybind11::arg("do_crop"), pybind11::arg("do_flip"), pybind11::arg("blur_p"),
+        pybind11::arg("blur_kernel"), pybind11::arg("sigma_lo"), pybind11::arg("sigma_hi"),
+        pybind11::arg("seed_t") = pybind11::none(), pybind11::arg("offs") = pybind11::none(),
+        pybind11::arg("hw") = pybind11::none(), pybind11::arg("rows") = 0);
 }
 
 }  // namespace sdx_bind

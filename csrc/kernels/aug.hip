@@ -11,6 +11,7 @@
 // Contrast needs the image mean at its position in the (random) jitter order, so the
 // pixel pipeline runs twice when contrast is active: pass 1 up to the contrast op
 // (block-reduced grey mean), pass 2 the full chain.
+#include "blur_plan.h"
 #include "common.h"
 #include "launchers.h"
 
@@ -180,25 +181,14 @@ __device__ void jitter_ops(const ViewParams& v, int n_ops, float cmean, float& r
   }
 }
 
-__global__ __launch_bounds__(256) void aug_kernel(AugParams p) {
-  __shared__ float red[4];
-  __shared__ ViewParams vp;
-  const int b = blockIdx.x, view = blockIdx.y;
-  const int64_t src = p.idx[b];
-  SDX_DCHECK(p.n_data <= 0 || (src >= 0 && src < p.n_data));
-  // dense [N][H][W][3] store, or native-resolution images (ImageFolder: RandomResizedCrop
-  // samples its box from the original pixels, as torchvision does on the decoded image)
-  const int H = p.offs ? p.hw[2 * src] : p.H, W = p.offs ? p.hw[2 * src + 1] : p.W;
-  const uint8_t* img = p.offs ? p.data + p.offs[src] : p.data + (size_t)src * p.H * p.W * 3;
-  if (threadIdx.x == 0) {
-    const uint64_t seed = p.seed_dev ? (uint64_t)p.seed_dev[0] : p.seed;
-    Rng rng{mix64(seed * 0x100000001b3ull + (uint64_t)src * 31ull + (uint64_t)view * 0x9E37ull + (uint64_t)b), 0};
-    make_view_params(p, rng, vp, H, W);
-  }
-  __syncthreads();
-  const ViewParams v = vp;
+// The per-pixel pipeline shared by aug_kernel and aug_blur_kernel: one copy, so a view the blur
+// kernel leaves un-blurred is bit-equal to aug_kernel's by construction.
+
+// pass 1: grey mean at the contrast position over the S x S pixels (0 when contrast is not
+// applied); `red`: 4 floats of LDS
+__device__ __forceinline__ float contrast_mean(const AugParams& p, const uint8_t* img, int H, int W,
+                                               const ViewParams& v, float* red) {
   const int npix = p.S * p.S;
-  // pass 1: grey mean at the contrast position (only if contrast is applied)
   float cmean = 0.f;
   int cpos = -1;
   if (v.jitter)
@@ -217,26 +207,219 @@ __global__ __launch_bounds__(256) void aug_kernel(AugParams p) {
     __syncthreads();
     cmean = (red[0] + red[1] + red[2] + red[3]) / (float)npix;
   }
-  uint16_t* out = p.out + ((size_t)view * p.B + b) * npix * 8;
+  return cmean;
+}
+
+// sample -> jitter -> gray: the colour pixel in [0, 1] before normalize
+__device__ __forceinline__ void colour_pixel(const AugParams& p, const uint8_t* img, int H, int W, const ViewParams& v,
+                                             float cmean, int oy, int ox, float& r, float& g, float& bb) {
+  sample_pixel(p, img, H, W, v, oy, ox, r, g, bb);
+  if (v.jitter) jitter_ops(v, 4, cmean, r, g, bb);
+  if (v.gray) { const float gy = grey(r, g, bb); r = g = bb = gy; }
+}
+
+// normalize, round to bf16 once, store the 16-byte pixel (channels 3..7 zero)
+__device__ __forceinline__ void store_pixel(const AugParams& p, uint16_t* out, int pix, float r, float g, float bb) {
+  r = (r - p.mean[0]) * p.inv_std[0];
+  g = (g - p.mean[1]) * p.inv_std[1];
+  bb = (bb - p.mean[2]) * p.inv_std[2];
+  reinterpret_cast<uint4*>(out)[pix] = make_uint4(pack_bf2(r, g), pack_bf2(bb, 0.f), 0u, 0u);
+}
+
+// pass 2 of a view without blur: every pixel straight from the source to the store
+__device__ __forceinline__ void plain_view(const AugParams& p, const uint8_t* img, int H, int W, const ViewParams& v,
+                                           float cmean, uint16_t* out) {
+  const int npix = p.S * p.S;
   for (int pix = threadIdx.x; pix < npix; pix += 256) {
     float r, g, bb;
-    sample_pixel(p, img, H, W, v, pix / p.S, pix % p.S, r, g, bb);
-    if (v.jitter) jitter_ops(v, 4, cmean, r, g, bb);
-    if (v.gray) { const float gy = grey(r, g, bb); r = g = bb = gy; }
-    r = (r - p.mean[0]) * p.inv_std[0];
-    g = (g - p.mean[1]) * p.inv_std[1];
-    bb = (bb - p.mean[2]) * p.inv_std[2];
-    reinterpret_cast<uint4*>(out)[pix] = make_uint4(pack_bf2(r, g), pack_bf2(bb, 0.f), 0u, 0u);
+    colour_pixel(p, img, H, W, v, cmean, pix / p.S, pix % p.S, r, g, bb);
+    store_pixel(p, out, pix, r, g, bb);
   }
 }
 
-}  // namespace
+__global__ __launch_bounds__(256) void aug_kernel(AugParams p) {
+  __shared__ float red[4];
+  __shared__ ViewParams vp;
+  const int b = blockIdx.x, view = blockIdx.y;
+  const int64_t src = p.idx[b];
+  SDX_DCHECK(p.n_data <= 0 || (src >= 0 && src < p.n_data));
+  // dense [N][H][W][3] store, or native-resolution images (ImageFolder: RandomResizedCrop
+  // samples its box from the original pixels, as torchvision does on the decoded image)
+  const int H = p.offs ? p.hw[2 * src] : p.H, W = p.offs ? p.hw[2 * src + 1] : p.W;
+  const uint8_t* img = p.offs ? p.data + p.offs[src] : p.data + (size_t)src * p.H * p.W * 3;
+  if (threadIdx.x == 0) {
+    const uint64_t seed = p.seed_dev ? (uint64_t)p.seed_dev[0] : p.seed;
+    Rng rng{mix64(seed * 0x100000001b3ull + (uint64_t)src * 31ull + (uint64_t)view * 0x9E37ull + (uint64_t)b), 0};
+    make_view_params(p, rng, vp, H, W);
+  }
+  __syncthreads();
+  const ViewParams v = vp;
+  const float cmean = contrast_mean(p, img, H, W, v, red);
+  const int npix = p.S * p.S;
+  plain_view(p, img, H, W, v, cmean, p.out + ((size_t)view * p.B + b) * npix * 8);
+}
 
-hipError_t launch_gpu_augment(const uint8_t* data, const int64_t* idx, int B, int H, int W, int S, int n_views,
-                              uint64_t seed, const float* mean, const float* std, float scale_lo, float scale_hi,
-                              float ratio_lo, float ratio_hi, float jitter_p, float bright, float contrast,
-                              float sat, float hue, float gray_p, int do_crop, int do_flip, const int64_t* seed_dev,
-                              void* out, hipStream_t s, long n_data, const int64_t* offs, const int32_t* hw) {
+// ---- Gaussian blur stage (SimCLR recipe at ImageNet-sized inputs) ---------------------------
+// RandomApply(GaussianBlur(k, sigma ~ U(lo, hi)), p) between grayscale and normalize, as the
+// torchvision tensor gaussian_blur: separable, taps w_j ~ exp(-0.5 (j/sigma)^2) normalised to
+// sum 1, reflect padding, no clamp. Two more draws per view after the gray draw, so every
+// earlier draw of the view is the same with the stage on or off.
+//
+// A blurred view is streamed through LDS top to bottom (sizes: blur_plan.h), `rows` rows per
+// round, fp32 from the uint8 source to the one bf16 rounding at the store:
+//   A  pre-blur pixels (sample -> jitter -> gray) of the next `rows` rows into `stage`
+//   B  their horizontal blur into slots (y % ring_rows) of `ring`
+//   C  the output rows whose 2r+1 ring rows are now complete: vertical blur, normalize, store
+// C of one round and A of the next touch disjoint buffers, so a round costs two barriers.
+// A view whose blur draw is false runs aug_kernel's pixel loop unchanged.
+struct BlurParams {
+  float blur_p, sig_lo, sig_hi;
+  int r, rows, ring_rows, strip, stage_w, w_floats;
+};
+
+__device__ __forceinline__ int reflect_idx(int i, int n) {
+  i = i < 0 ? -i : i;
+  return i > n - 1 ? 2 * (n - 1) - i : i;
+}
+
+__global__ __launch_bounds__(256) void aug_blur_kernel(AugParams p, BlurParams q) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  __shared__ float red[4];
+  __shared__ ViewParams vp;
+  __shared__ float sigma_sh;   // < 0: this view is not blurred
+  const int b = blockIdx.x, view = blockIdx.y;
+  const int64_t src = p.idx[b];
+  SDX_DCHECK(p.n_data <= 0 || (src >= 0 && src < p.n_data));
+  const int H = p.offs ? p.hw[2 * src] : p.H, W = p.offs ? p.hw[2 * src + 1] : p.W;
+  const uint8_t* img = p.offs ? p.data + p.offs[src] : p.data + (size_t)src * p.H * p.W * 3;
+  if (threadIdx.x == 0) {
+    const uint64_t seed = p.seed_dev ? (uint64_t)p.seed_dev[0] : p.seed;
+    Rng rng{mix64(seed * 0x100000001b3ull + (uint64_t)src * 31ull + (uint64_t)view * 0x9E37ull + (uint64_t)b), 0};
+    make_view_params(p, rng, vp, H, W);
+    const bool blur = rng.uni() < q.blur_p;
+    const float sg = q.sig_lo + (q.sig_hi - q.sig_lo) * rng.uni();
+    sigma_sh = blur ? sg : -1.f;
+  }
+  __syncthreads();
+  // read in place: with dynamic LDS in the kernel a private copy's order[] (indexed at run
+  // time) would live in scratch
+  const ViewParams& v = vp;
+  const float sigma = sigma_sh;
+  const int S = p.S, npix = S * S;
+  // pass 1 runs over the un-blurred pixels, and a view whose blur draw is false is aug_kernel's
+  const float cmean = contrast_mean(p, img, H, W, v, red);
+  uint16_t* out = p.out + ((size_t)view * p.B + b) * npix * 8;
+  if (sigma < 0.f) {
+    plain_view(p, img, H, W, v, cmean, out);
+    return;
+  }
+
+  const int R = q.r, K = 2 * q.r + 1, rows = q.rows, ring_rows = q.ring_rows, strip = q.strip, sw = q.stage_w;
+  float* w = lds;                         // [R + 1] w[|j|]
+  float* stage = lds + q.w_floats;        // [rows][3][sw]
+  float* ring = stage + rows * 3 * sw;    // [ring_rows][3][strip]
+  for (int j = threadIdx.x; j <= R; j += 256) {
+    const float t = (float)j / sigma;
+    w[j] = expf(-0.5f * t * t);
+  }
+  __syncthreads();
+  // every thread adds the taps in the same order (-R..R): one deterministic normaliser
+  float wsum = 0.f;
+  for (int j = -R; j <= R; ++j) wsum += w[j < 0 ? -j : j];
+  __syncthreads();
+  for (int j = threadIdx.x; j <= R; j += 256) w[j] = w[j] / wsum;
+  __syncthreads();
+
+  const int n_rounds = (S + rows - 1) / rows;
+  for (int x0 = 0; x0 < S; x0 += strip) {
+    const int tw = min(strip, S - x0);                        // output columns of this strip
+    const int xa = max(0, x0 - R), xb = min(S, x0 + tw + R);  // staged columns [xa, xb)
+    const int pw = xb - xa;
+    SDX_DCHECK(pw <= sw && tw <= strip);
+    int o_next = 0;   // first output row not yet stored
+    for (int n = 0; n <= n_rounds; ++n) {
+      if (n < n_rounds) {   // A
+        const int y0 = n * rows, nr = min(rows, S - y0);
+        for (int i = threadIdx.x; i < nr * pw; i += 256) {
+          const int rr = i / pw, t = i - rr * pw;
+          float r, g, bb;
+          colour_pixel(p, img, H, W, v, cmean, y0 + rr, xa + t, r, g, bb);
+          SDX_DCHECK(rr >= 0 && rr < rows && t >= 0 && t < sw);
+          float* d = stage + rr * 3 * sw + t;
+          d[0] = r; d[sw] = g; d[2 * sw] = bb;
+        }
+      }
+      if (n > 0) {   // C: rows up to y1 are in the ring
+        const int y1 = min(n * rows, S) - 1;
+        const int o_end = y1 == S - 1 ? S : y1 - R + 1;
+        const int cnt = max(0, o_end - o_next);
+        for (int i = threadIdx.x; i < cnt * tw; i += 256) {
+          const int oo = i / tw, t = i - oo * tw;
+          const int o = o_next + oo;
+          float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+          if (o - R >= 0 && o + R <= S - 1) {
+            SDX_DCHECK(o - R > y1 - ring_rows && o + R <= y1);
+            int s = (o - R) % ring_rows;
+            for (int j = 0; j < K; ++j) {
+              const float wj = w[j < R ? R - j : j - R];
+              const float* row = ring + s * 3 * strip + t;
+              a0 += wj * row[0]; a1 += wj * row[strip]; a2 += wj * row[2 * strip];
+              if (++s == ring_rows) s = 0;
+            }
+          } else {
+            for (int j = -R; j <= R; ++j) {
+              const int yy = reflect_idx(o + j, S);
+              SDX_DCHECK(yy >= 0 && yy < S && yy > y1 - ring_rows && yy <= y1);
+              const float wj = w[j < 0 ? -j : j];
+              const float* row = ring + (yy % ring_rows) * 3 * strip + t;
+              a0 += wj * row[0]; a1 += wj * row[strip]; a2 += wj * row[2 * strip];
+            }
+          }
+          SDX_DCHECK(o >= 0 && o < S && x0 + t < S);
+          store_pixel(p, out, o * S + x0 + t, a0, a1, a2);
+        }
+        o_next += cnt;
+      }
+      if (n == n_rounds) break;
+      __syncthreads();
+      {   // B
+        const int y0 = n * rows, nr = min(rows, S - y0);
+        for (int i = threadIdx.x; i < nr * tw; i += 256) {
+          const int rr = i / tw, t = i - rr * tw;
+          const int x = x0 + t;
+          const float* srow = stage + rr * 3 * sw;
+          float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+          if (x - R >= 0 && x + R <= S - 1) {
+            const float* sp = srow + (x - R - xa);
+            SDX_DCHECK(x - R - xa >= 0 && x + R - xa < pw);
+            for (int j = 0; j < K; ++j) {
+              const float wj = w[j < R ? R - j : j - R];
+              a0 += wj * sp[j]; a1 += wj * sp[sw + j]; a2 += wj * sp[2 * sw + j];
+            }
+          } else {
+            for (int j = -R; j <= R; ++j) {
+              const int u = reflect_idx(x + j, S) - xa;
+              SDX_DCHECK(u >= 0 && u < pw);
+              const float wj = w[j < 0 ? -j : j];
+              a0 += wj * srow[u]; a1 += wj * srow[sw + u]; a2 += wj * srow[2 * sw + u];
+            }
+          }
+          const int s = (y0 + rr) % ring_rows;
+          SDX_DCHECK(s >= 0 && s < ring_rows && t < strip);
+          float* d = ring + s * 3 * strip + t;
+          d[0] = a0; d[strip] = a1; d[2 * strip] = a2;
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+
+AugParams make_params(const uint8_t* data, const int64_t* idx, int B, int H, int W, int S, int n_views, uint64_t seed,
+                      const float* mean, const float* std, float scale_lo, float scale_hi, float ratio_lo,
+                      float ratio_hi, float jitter_p, float bright, float contrast, float sat, float hue, float gray_p,
+                      int do_crop, int do_flip, const int64_t* seed_dev, void* out, long n_data, const int64_t* offs,
+                      const int32_t* hw) {
   AugParams p{};
   p.offs = offs;
   p.hw = hw;
@@ -248,7 +431,61 @@ hipError_t launch_gpu_augment(const uint8_t* data, const int64_t* idx, int B, in
   p.jitter_p = jitter_p; p.bright = bright; p.contrast = contrast; p.sat = sat; p.hue = hue; p.gray_p = gray_p;
   p.do_crop = do_crop; p.do_flip = do_flip;
   p.seed_dev = seed_dev;
+  return p;
+}
+
+}  // namespace
+
+hipError_t launch_gpu_augment(const uint8_t* data, const int64_t* idx, int B, int H, int W, int S, int n_views,
+                              uint64_t seed, const float* mean, const float* std, float scale_lo, float scale_hi,
+                              float ratio_lo, float ratio_hi, float jitter_p, float bright, float contrast,
+                              float sat, float hue, float gray_p, int do_crop, int do_flip, const int64_t* seed_dev,
+                              void* out, hipStream_t s, long n_data, const int64_t* offs, const int32_t* hw) {
+  const AugParams p = make_params(data, idx, B, H, W, S, n_views, seed, mean, std, scale_lo, scale_hi, ratio_lo,
+                                  ratio_hi, jitter_p, bright, contrast, sat, hue, gray_p, do_crop, do_flip, seed_dev,
+                                  out, n_data, offs, hw);
   hipLaunchKernelGGL(aug_kernel, dim3(B, n_views), dim3(256), 0, s, p);
+  SDX_LAUNCH_CHECK();
+  return hipSuccess;
+}
+
+// The same launch with the blur stage (one workgroup per (sample, view), one launch for the
+// batch). blur_k 0 = automatic, rows 0 = automatic (blur_plan.h); a request the plan refuses
+// is hipErrorInvalidValue, never a launch of something else.
+hipError_t launch_gpu_augment_blur(const uint8_t* data, const int64_t* idx, int B, int H, int W, int S, int n_views,
+                                   uint64_t seed, const float* mean, const float* std, float scale_lo,
+                                   float scale_hi, float ratio_lo, float ratio_hi, float jitter_p, float bright,
+                                   float contrast, float sat, float hue, float gray_p, int do_crop, int do_flip,
+                                   float blur_p, int blur_k, float sigma_lo, float sigma_hi, int rows,
+                                   const int64_t* seed_dev, void* out, hipStream_t s, long n_data,
+                                   const int64_t* offs, const int32_t* hw) {
+  sdx_blur::Plan pl{};
+  if (!sdx_blur::make_plan(S, blur_k, rows, &pl) || !(sigma_lo > 0.f) || !(sigma_lo <= sigma_hi))
+    return hipErrorInvalidValue;
+  const AugParams p = make_params(data, idx, B, H, W, S, n_views, seed, mean, std, scale_lo, scale_hi, ratio_lo,
+                                  ratio_hi, jitter_p, bright, contrast, sat, hue, gray_p, do_crop, do_flip, seed_dev,
+                                  out, n_data, offs, hw);
+  BlurParams q{};
+  q.blur_p = blur_p; q.sig_lo = sigma_lo; q.sig_hi = sigma_hi;
+  q.r = pl.r; q.rows = pl.rows; q.ring_rows = pl.ring_rows; q.strip = pl.strip; q.stage_w = pl.stage_w;
+  q.w_floats = pl.w_floats;
+  if (pl.lds_bytes > sdx_blur::kLdsDefault) {
+    // above 64 KiB the kernel's dynamic-LDS limit has to be raised (once per device: to the most
+    // any plan can ask for). `raised` is only a cache and is not synchronised: two threads racing
+    // on it at worst both set the attribute to the same value.
+    static bool raised[64] = {};
+    int dev = 0;
+    if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
+    if (dev < 0 || dev >= 64 || !raised[dev]) {
+      if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(aug_blur_kernel),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             (int)(sdx_blur::kLdsPerCu - sdx_blur::kStaticLds));
+          e != hipSuccess)
+        return e;
+      if (dev >= 0 && dev < 64) raised[dev] = true;
+    }
+  }
+  hipLaunchKernelGGL(aug_blur_kernel, dim3(B, n_views), dim3(256), (size_t)pl.lds_bytes, s, p, q);
   SDX_LAUNCH_CHECK();
   return hipSuccess;
 }

@@ -10,7 +10,8 @@ Additions (new flags only; no reference flag changes meaning):
 ``--precision``, ``--backend``, ``--synthetic``, ``--stem``, ``--optimizer {sgd,lars}``,
 ``--grad_semantics {ref,exact}`` (Q2), ``--dist_backend``, ``--seed``, ``--head``,
 ``--feat_dim`` (Q11), ``--resume``, ``--cuda_graph``, ``--work_dir``,
-``--knn_freq`` / ``--knn`` with ``--knn_k`` / ``--knn_t`` (weighted k-NN monitor, engine/knn.py).
+``--knn_freq`` / ``--knn`` with ``--knn_k`` / ``--knn_t`` (weighted k-NN monitor, engine/knn.py),
+``--blur_p`` / ``--blur_kernel`` / ``--blur_sigma`` (Gaussian-blur augmentation, data/augment.py).
 Fixes: ``--num_workers`` is honoured (Q6): it sizes the image-decode thread pool of
 ``dataset=path`` and the CPU augmentation threads of ``--gpu_aug 0`` (the default pipeline
 is the GPU kernel, which needs no workers); ``dataset=path`` parses ``--mean/--std``
@@ -149,6 +150,13 @@ def pretrain_parser() -> argparse.ArgumentParser:
                    help="weighted k-NN accuracy of the encoder on the validation split every N epochs and "
                         "after the last epoch (0 = off)")
     _add_knn_flags(g)
+    g.add_argument("--blur_p", type=float, default=0.0,
+                   help="probability of the Gaussian-blur augmentation after grayscale (SimCLR's ImageNet "
+                        "recipe uses 0.5; 0 = off, the CIFAR recipe)")
+    g.add_argument("--blur_kernel", type=int, default=0,
+                   help="blur kernel size, odd (0 = 10%% of --size, made odd, at least 3)")
+    g.add_argument("--blur_sigma", type=float, nargs=2, default=[0.1, 2.0], metavar=("LO", "HI"),
+                   help="blur sigma is drawn uniformly from [LO, HI]")
     _add_common_new_flags(p)
     return p
 
@@ -193,6 +201,9 @@ def parse_pretrain(argv: Optional[Sequence[str]] = None, make_dirs: bool = True,
     if opt.knn_freq > 0 and opt.dataset == "path":
         raise ValueError("--knn_freq needs a dataset with a validation split (cifar10, cifar100 or --synthetic); "
                          "--dataset path has none")
+    opt.blur_sigma = tuple(opt.blur_sigma)
+    if not 0.0 <= opt.blur_p <= 1.0 or opt.blur_kernel < 0 or not 0.0 < opt.blur_sigma[0] <= opt.blur_sigma[1]:
+        raise ValueError("--blur_p in [0, 1], --blur_kernel >= 0 and --blur_sigma 0 < LO <= HI are required")
     rank, local_rank, world = env_rank_info(opt.local_rank)
     opt.rank, opt.local_rank = rank, local_rank
     if opt.ngpu is None:

@@ -40,6 +40,45 @@ class _Rng:
         return float(np.float32((v >> 40) * (1.0 / 16777216.0)))
 
 
+# ---- the LDS plan of the blur kernel: mirror of csrc/include/blur_plan.h -------------------
+BLUR_LDS_PER_CU = 160 * 1024
+_BLUR_STATIC_LDS = 256
+_BLUR_MIN_STRIP = 64
+_BLUR_MAX_ROWS = 16
+
+
+def blur_auto_kernel(size: int) -> int:
+    return max(3, (size // 10) | 1)
+
+
+def _blur_lds_bytes(S, k, rows, strip):
+    w = ((k - 1) // 2 + 1 + 3) // 4 * 4
+    return 4 * (w + 3 * (rows * min(S, strip + k - 1) + (k + rows - 1) * strip))
+
+
+def blur_plan(S: int, k: int = 0, rows: int = 0):
+    """dict(k, rows, strip, n_strips, lds_bytes) of the blur kernel, or None when the request
+    cannot be served (k even or < 3, radius beyond S - 1, no fit in the LDS)."""
+    if S < 1 or S > (1 << 15) or k < 0 or k > (1 << 15) or rows < 0 or rows > _BLUR_MAX_ROWS:
+        return None
+    k = k or blur_auto_kernel(S)
+    if k < 3 or k % 2 == 0 or (k - 1) // 2 > S - 1:
+        return None
+    budget = BLUR_LDS_PER_CU - _BLUR_STATIC_LDS
+    if rows == 0:
+        fit = [c for c in (4, 2, 1) if _blur_lds_bytes(S, k, c, S) <= BLUR_LDS_PER_CU // 2 - _BLUR_STATIC_LDS] or \
+              [c for c in (4, 2, 1) if _blur_lds_bytes(S, k, c, S) <= budget] or [1]
+        rows = fit[0]
+    n, strip = 1, S
+    while _blur_lds_bytes(S, k, rows, strip) > budget:
+        n += 1
+        strip = (S + n - 1) // n
+        if strip < min(S, _BLUR_MIN_STRIP):
+            return None
+    return dict(k=k, rows=rows, strip=strip, n_strips=(S + strip - 1) // strip,
+                lds_bytes=_blur_lds_bytes(S, k, rows, strip))
+
+
 @dataclass
 class AugConfig:
     size: int = 32
@@ -56,10 +95,36 @@ class AugConfig:
     flip: bool = True
     mean: Sequence[float] = (0.4914, 0.4822, 0.4465)
     std: Sequence[float] = (0.2023, 0.1994, 0.2010)
+    # RandomApply(GaussianBlur(blur_kernel, sigma ~ U(blur_sigma)), p=blur_p) after grayscale
+    # (the SimCLR recipe for ImageNet-sized inputs); off by default
+    blur_p: float = 0.0
+    blur_kernel: int = 0          # 0 = automatic: 10 % of the side, odd, at least 3
+    blur_sigma: Sequence[float] = (0.1, 2.0)
+
+    def __post_init__(self):
+        if self.blur_p == 0:
+            return
+        if not 0.0 < self.blur_p <= 1.0:
+            raise ValueError(f"blur_p {self.blur_p} must be in [0, 1]")
+        k, S = self.blur_k, self.size
+        if k < 3 or k % 2 == 0:
+            raise ValueError(f"blur_kernel {k} must be odd and >= 3")
+        if (k - 1) // 2 > S - 1:
+            raise ValueError(f"blur radius {(k - 1) // 2} exceeds size - 1 = {S - 1}: reflect padding is undefined")
+        if len(self.blur_sigma) != 2 or not 0.0 < self.blur_sigma[0] <= self.blur_sigma[1]:
+            raise ValueError(f"blur_sigma {tuple(self.blur_sigma)} needs 0 < lo <= hi")
+        if blur_plan(S, k) is None:
+            raise ValueError(f"blur of kernel size {k} at size {S} does not fit the {BLUR_LDS_PER_CU // 1024} KiB LDS")
+
+    @property
+    def blur_k(self) -> int:
+        """The kernel size in effect."""
+        return self.blur_kernel if self.blur_kernel else blur_auto_kernel(self.size)
 
     @staticmethod
-    def simclr(size, mean, std):
-        return AugConfig(size=size, mean=mean, std=std)
+    def simclr(size, mean, std, blur_p=0.0, blur_kernel=0, blur_sigma=(0.1, 2.0)):
+        return AugConfig(size=size, mean=mean, std=std, blur_p=blur_p, blur_kernel=blur_kernel,
+                         blur_sigma=tuple(blur_sigma))
 
     @staticmethod
     def linear_train(size, mean, std):
@@ -75,11 +140,20 @@ class AugConfig:
 
 
 def gpu_augment(data: torch.Tensor, idx: torch.Tensor, cfg: AugConfig, seed, seed_t=None, offs=None,
-                hw=None) -> torch.Tensor:
+                hw=None, _blur_rows: int = 0) -> torch.Tensor:
     """``seed_t``: optional int64 device scalar read by the kernel at run time (graph replays).
     ``offs``/``hw``: a ragged native-resolution store (``data`` flat uint8, int64 byte
-    offsets, int32 [N, 2] sizes; data/datasets.py load_image_folder)."""
+    offsets, int32 [N, 2] sizes; data/datasets.py load_image_folder).
+    ``cfg.blur_p > 0`` runs the kernel with the blur stage. ``_blur_rows`` is not part of the
+    interface: rows per barrier round (0 = the plan's choice), for tools/aug_blur_bench.py and the
+    tests only; it schedules the stream through LDS and never changes the output."""
     m = _ext.require()
+    if cfg.blur_p > 0:
+        return m.gpu_augment_blur(data, idx, cfg.size, cfg.n_views, int(seed) & ((1 << 63) - 1), list(cfg.mean),
+                                  list(cfg.std), cfg.scale[0], cfg.scale[1], cfg.ratio[0], cfg.ratio[1],
+                                  cfg.jitter_p, cfg.brightness, cfg.contrast, cfg.saturation, cfg.hue, cfg.gray_p,
+                                  cfg.crop, cfg.flip, cfg.blur_p, cfg.blur_k, cfg.blur_sigma[0], cfg.blur_sigma[1],
+                                  seed_t, offs, hw, _blur_rows)
     return m.gpu_augment(data, idx, cfg.size, cfg.n_views, int(seed) & ((1 << 63) - 1), list(cfg.mean),
                          list(cfg.std), cfg.scale[0], cfg.scale[1], cfg.ratio[0], cfg.ratio[1], cfg.jitter_p,
                          cfg.brightness, cfg.contrast, cfg.saturation, cfg.hue, cfg.gray_p, cfg.crop, cfg.flip,
@@ -126,8 +200,24 @@ def _view_params(cfg: AugConfig, H: int, W: int, rng: _Rng):
     gray = rng.uni() < cfg.gray_p
     if cfg.brightness <= 0 and cfg.contrast <= 0 and cfg.saturation <= 0 and cfg.hue <= 0:
         jitter = False
+    # the blur draws come last, so every draw above is the same with the stage on or off
+    blur = rng.uni() < cfg.blur_p
+    sigma = cfg.blur_sigma[0] + (cfg.blur_sigma[1] - cfg.blur_sigma[0]) * rng.uni()
     return dict(ci=ci, cj=cj, ch=ch, cw=cw, flip=flip, jitter=jitter, fb=fb, fc=fc, fs=fs, fh=fh, order=order,
-                gray=gray)
+                gray=gray, blur=blur, sigma=sigma)
+
+
+def _gaussian_blur(c: torch.Tensor, k: int, sigma: float) -> torch.Tensor:
+    """torchvision's tensor gaussian_blur on [3, S, S] fp32: separable, reflect padding."""
+    r = (k - 1) // 2
+    x = torch.arange(-r, r + 1, dtype=torch.float32)
+    w = torch.exp(-0.5 * (x / sigma) ** 2)
+    w = w / w.sum()
+    S = c.shape[-1]
+    pad = F.pad(c.unsqueeze(0), (r, r, 0, 0), mode="reflect")[0]
+    c = sum(w[j] * pad[:, :, j:j + S] for j in range(k))
+    pad = F.pad(c.unsqueeze(0), (0, 0, r, r), mode="reflect")[0]
+    return sum(w[j] * pad[:, j:j + S, :] for j in range(k))
 
 
 def _grey(img):
@@ -210,6 +300,8 @@ def augment_reference(data: torch.Tensor, idx: torch.Tensor, cfg: AugConfig, see
                         c = _hue(c, p["fh"])
             if p["gray"]:
                 c = _grey(c).unsqueeze(0).expand(3, S, S)
+            if p["blur"]:
+                c = _gaussian_blur(c, cfg.blur_k, p["sigma"])
             mean_t = torch.tensor(cfg.mean).view(3, 1, 1)
             std_t = torch.tensor(cfg.std).view(3, 1, 1)
             c = (c - mean_t) / std_t

@@ -166,7 +166,9 @@ class PretrainEngine:
         self.data_hw = torch.from_numpy(ds.sizes).to(dev) if ds.ragged else None
         self.labels = torch.from_numpy(ds.labels).to(dev)
         self.sampler = DistributedIndexSampler(len(ds), opt.local_batch, world, rank, seed=opt.seed)
-        self.aug = AugConfig.simclr(opt.size, opt.mean_t, opt.std_t)
+        self.aug = AugConfig.simclr(opt.size, opt.mean_t, opt.std_t, blur_p=getattr(opt, "blur_p", 0.0),
+                                    blur_kernel=getattr(opt, "blur_kernel", 0),
+                                    blur_sigma=getattr(opt, "blur_sigma", (0.1, 2.0)))
         self.logger = None
         if rank == 0:
             from ..utils.tb import Logger
