@@ -112,6 +112,23 @@ torch::Tensor gpu_augment_blur(torch::Tensor data, torch::Tensor idx, int64_t S,
   return out;
 }
 
+// The evaluation transform (aug.hip eval_crop_kernel): Resize(resize) on the shorter side,
+// antialiased bilinear, CenterCrop(S), normalize; one view of every idx image, no draws.
+torch::Tensor gpu_eval_crop(torch::Tensor data, torch::Tensor idx, int64_t S, int64_t resize,
+                            std::vector<double> mean, std::vector<double> std, c10::optional<torch::Tensor> offs,
+                            c10::optional<torch::Tensor> hw) {
+  TORCH_CHECK(S >= 1, "crop size must be >= 1, got ", S);
+  TORCH_CHECK(resize >= S && resize <= 32768, "resize must be in [S, 32768] = [", S, ", 32768], got ", resize);
+  const AugArgs a = check_aug_args(data, idx, S, 1, mean, std, c10::nullopt, offs, hw);
+  TORCH_CHECK(a.ragged || (a.H >= 1 && a.W >= 1), "data has no pixels");
+  c10::DeviceGuard dg(data.device());
+  auto out = torch::empty({a.B, S, S, 8}, data.options().dtype(at::kBFloat16));
+  check_hip(launch_gpu_eval_crop(data.data_ptr<uint8_t>(), idx.data_ptr<int64_t>(), (int)a.B, a.H, a.W, (int)S,
+                                 (int)resize, a.mean, a.std, out.data_ptr(), cur_stream(), a.n_data, a.offs, a.hw),
+            "gpu_eval_crop");
+  return out;
+}
+
 }  // namespace
 
 void register_data(pybind11::module& m) {
@@ -133,6 +150,11 @@ void register_data(pybind11::module& m) {
         pybind11::arg("blur_kernel"), pybind11::arg("sigma_lo"), pybind11::arg("sigma_hi"),
         pybind11::arg("seed_t") = pybind11::none(), pybind11::arg("offs") = pybind11::none(),
         pybind11::arg("hw") = pybind11::none(), pybind11::arg("rows") = 0);
+  m.def("gpu_eval_crop", &gpu_eval_crop,
+        "Resize(resize) on the shorter side + CenterCrop(S) + normalize -> NHWC bf16 (C padded to 8)",
+        pybind11::arg("data"), pybind11::arg("idx"), pybind11::arg("S"), pybind11::arg("resize"),
+        pybind11::arg("mean"), pybind11::arg("std"), pybind11::arg("offs") = pybind11::none(),
+        pybind11::arg("hw") = pybind11::none());
 }
 
 }  // namespace sdx_bind

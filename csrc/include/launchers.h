@@ -251,6 +251,11 @@ hipError_t launch_gpu_augment_blur(const uint8_t* data, const int64_t* idx, int 
                                    float blur_p, int blur_k, float sigma_lo, float sigma_hi, int rows,
                                    const int64_t* seed_dev, void* out, hipStream_t s, long n_data = 0,
                                    const int64_t* offs = nullptr, const int32_t* hw = nullptr);
+// Evaluation transform: Resize(R) on the shorter side (antialiased bilinear) + CenterCrop(S) +
+// normalize, one view, out [B][S][S][8] bf16. hipErrorInvalidValue unless 1 <= S <= R <= 32768.
+hipError_t launch_gpu_eval_crop(const uint8_t* data, const int64_t* idx, int B, int H, int W, int S, int R,
+                                const float* mean, const float* std, void* out, hipStream_t s, long n_data = 0,
+                                const int64_t* offs = nullptr, const int32_t* hw = nullptr);
 
 // ---- optimizers (optim.hip) -----------------------------------------------------
 hipError_t launch_sgd(float* p, const float* g, float* buf, long n, const float* lr, float momentum, float wd,

@@ -415,6 +415,123 @@ __global__ __launch_bounds__(256) void aug_blur_kernel(AugParams p, BlurParams q
   }
 }
 
+// ---- evaluation transform: Resize(R) on the shorter side + CenterCrop(S) + normalize ----------
+// The torchvision evaluation pipeline over the resident store (dense or ragged), one view, no
+// draws. Resize is the antialiased bilinear (triangle) filter of
+// F.interpolate(mode="bilinear", antialias=True): for an axis n_in -> n_out and output i,
+//   scale = n_in / n_out, support = max(scale, 1), c = scale (i + 0.5),
+//   taps j in [max(0, floor(c - support + 0.5)), min(n_in, floor(c + support + 0.5))),
+//   weight max(0, 1 - |j - c + 0.5| / support), divided by the sum over the window.
+// Window bounds and the tap offsets are exact integers over 2 n_out (so every implementation
+// agrees on every window, and the weights carry no error of a rounded centre): with
+// sup = max(n_in, n_out), a = (2i + 1) n_in + n_out,
+//   lo = floor((a - 2 sup) / (2 n_out)), hi = floor((a + 2 sup) / (2 n_out)), clamped, and tap j
+//   weighs 1 - |2 j n_out + n_out - (2i + 1) n_in| / (2 sup).
+// At scale 1 the window is {i, i + 1} with weights {1, 0}: the resample is the identity, and the
+// pixel reaches store_pixel as value * (1/255) exactly as aug_kernel's un-cropped sample does.
+// fp32 from the uint8 source to the one bf16 rounding; no uint8 intermediate image.
+//
+// Grid (image, band of kEvalBand output rows), 256 threads. The band's vertical windows are
+// worked out once into static LDS (their size does not depend on the scale); a thread owns
+// output columns (its horizontal window is worked out once per column) and walks the band's
+// rows: per source row of the vertical window the horizontal window, all in registers. Every
+// loop is bounded by the image's own H and W, whatever the scale.
+constexpr int kEvalBand = 24;   // 224 rows: 9 bands and a partial one
+
+struct AxisTaps {
+  int lo, hi;       // source taps [lo, hi), inside [0, n_in)
+  int num0;         // 2 lo n_out + n_out - (2i + 1) n_in; tap j: num0 + 2 (j - lo) n_out
+  float inv_sum;    // 1 / sum of the window's weights
+};
+
+__device__ __forceinline__ float tap_weight(int num, float k) { return fmaxf(0.f, 1.f - fabsf((float)num) * k); }
+
+// window of output coordinate i of an axis n_in -> n_out (1 <= n_in, 0 <= i < n_out);
+// k = 1 / (2 max(n_in, n_out))
+__device__ __forceinline__ AxisTaps axis_taps(int n_in, int n_out, int i, float k) {
+  const int64_t sup2 = 2 * (int64_t)max(n_in, n_out);
+  const int64_t a = (int64_t)(2 * (int64_t)i + 1) * n_in + n_out;
+  const int64_t d = 2 * (int64_t)n_out;
+  int64_t lo, hi;
+  if (a + sup2 < (int64_t)1 << 31) {   // the 32-bit divide is several times cheaper
+    lo = a > sup2 ? (uint32_t)(a - sup2) / (uint32_t)d : 0;
+    hi = (uint32_t)(a + sup2) / (uint32_t)d;
+  } else {
+    lo = a > sup2 ? (a - sup2) / d : 0;
+    hi = (a + sup2) / d;
+  }
+  AxisTaps t;
+  t.lo = (int)min(lo, (int64_t)n_in - 1);
+  t.hi = (int)min(hi, (int64_t)n_in);
+  t.hi = max(t.hi, t.lo + 1);
+  t.num0 = (int)(t.lo * d + n_out - (2 * (int64_t)i + 1) * n_in);
+  float sum = 0.f;
+  int num = t.num0;
+  for (int j = t.lo; j < t.hi; ++j, num += (int)d) sum += tap_weight(num, k);
+  t.inv_sum = 1.f / sum;
+  return t;
+}
+
+// torchvision's CenterCrop offset int(round(d / 2.0)): half to even
+__device__ __forceinline__ int crop_offset(int d) {
+  int t = d >> 1;
+  if ((d & 1) && (t & 1)) ++t;
+  return t;
+}
+
+__global__ __launch_bounds__(256) void eval_crop_kernel(AugParams p, int R, int cw_log2) {
+  __shared__ AxisTaps ytaps[kEvalBand];
+  const int b = blockIdx.x;
+  const int64_t src = p.idx[b];
+  SDX_DCHECK(p.n_data <= 0 || (src >= 0 && src < p.n_data));
+  const int H = p.offs ? p.hw[2 * src] : p.H, W = p.offs ? p.hw[2 * src + 1] : p.W;
+  const uint8_t* img = p.offs ? p.data + p.offs[src] : p.data + (size_t)src * p.H * p.W * 3;
+  SDX_DCHECK(H >= 1 && W >= 1);
+  if (H < 1 || W < 1) return;   // a malformed store entry: nothing to read
+  const int S = p.S;
+  // resized size: the shorter side becomes R, the longer floor(R long / short); never past
+  // int (an absurd aspect would only distort, not read out of bounds: the taps are clamped)
+  const int64_t lng = (int64_t)R * max(H, W) / min(H, W);
+  const int ol = (int)min(lng, (int64_t)0x3fffffff);
+  const int oh = H <= W ? R : ol, ow = H <= W ? ol : R;
+  const int top = crop_offset(oh - S), left = crop_offset(ow - S);
+  const float ky = 0.5f / (float)max(H, oh), kx = 0.5f / (float)max(W, ow);
+
+  const int y0 = blockIdx.y * kEvalBand, nrows = min(kEvalBand, S - y0);
+  if ((int)threadIdx.x < nrows) ytaps[threadIdx.x] = axis_taps(H, oh, top + y0 + (int)threadIdx.x, ky);
+  __syncthreads();
+
+  const int cw = 1 << cw_log2;            // threads across a row; 256 / cw rows at a time
+  const int tx = threadIdx.x & (cw - 1), ty = threadIdx.x >> cw_log2, rstep = 256 >> cw_log2;
+  const int dx = 2 * ow, dy = 2 * oh;
+  uint16_t* out = p.out + (size_t)b * S * S * 8;
+  for (int x = tx; x < S; x += cw) {
+    const AxisTaps xt = axis_taps(W, ow, left + x, kx);
+    SDX_DCHECK(xt.lo >= 0 && xt.lo < xt.hi && xt.hi <= W);
+    for (int r = ty; r < nrows; r += rstep) {
+      const AxisTaps yt = ytaps[r];
+      SDX_DCHECK(yt.lo >= 0 && yt.lo < yt.hi && yt.hi <= H);
+      float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+      int ny = yt.num0;
+      for (int j = yt.lo; j < yt.hi; ++j, ny += dy) {
+        const uint8_t* row = img + ((size_t)j * W + xt.lo) * 3;
+        float h0 = 0.f, h1 = 0.f, h2 = 0.f;
+        int nx = xt.num0;
+        for (int i = xt.lo; i < xt.hi; ++i, nx += dx, row += 3) {
+          const float wx = tap_weight(nx, kx);
+          h0 += wx * (float)row[0]; h1 += wx * (float)row[1]; h2 += wx * (float)row[2];
+        }
+        const float wy = tap_weight(ny, ky);
+        a0 += wy * h0; a1 += wy * h1; a2 += wy * h2;
+      }
+      const float nrm = xt.inv_sum * yt.inv_sum;
+      SDX_DCHECK(y0 + r < S && x < S);
+      store_pixel(p, out, (y0 + r) * S + x, a0 * nrm * (1.f / 255.f), a1 * nrm * (1.f / 255.f),
+                  a2 * nrm * (1.f / 255.f));
+    }
+  }
+}
+
 AugParams make_params(const uint8_t* data, const int64_t* idx, int B, int H, int W, int S, int n_views, uint64_t seed,
                       const float* mean, const float* std, float scale_lo, float scale_hi, float ratio_lo,
                       float ratio_hi, float jitter_p, float bright, float contrast, float sat, float hue, float gray_p,
@@ -486,6 +603,21 @@ hipError_t launch_gpu_augment_blur(const uint8_t* data, const int64_t* idx, int 
     }
   }
   hipLaunchKernelGGL(aug_blur_kernel, dim3(B, n_views), dim3(256), (size_t)pl.lds_bytes, s, p, q);
+  SDX_LAUNCH_CHECK();
+  return hipSuccess;
+}
+
+// Resize(R) on the shorter side + CenterCrop(S) + normalize of B images (eval_crop_kernel): one
+// view, out [B][S][S][8]. 1 <= S <= R <= 32768, else hipErrorInvalidValue.
+hipError_t launch_gpu_eval_crop(const uint8_t* data, const int64_t* idx, int B, int H, int W, int S, int R,
+                                const float* mean, const float* std, void* out, hipStream_t s, long n_data,
+                                const int64_t* offs, const int32_t* hw) {
+  if (B < 1 || S < 1 || S > R || R > 32768 || (!offs && (H < 1 || W < 1))) return hipErrorInvalidValue;
+  const AugParams p = make_params(data, idx, B, H, W, S, 1, 0, mean, std, 1.f, 1.f, 1.f, 1.f, 0.f, 0.f, 0.f, 0.f, 0.f,
+                                  0.f, 0, 0, nullptr, out, n_data, offs, hw);
+  int cw_log2 = 0;
+  while (cw_log2 < 8 && (1 << cw_log2) < S) ++cw_log2;
+  hipLaunchKernelGGL(eval_crop_kernel, dim3(B, (S + kEvalBand - 1) / kEvalBand), dim3(256), 0, s, p, R, cw_log2);
   SDX_LAUNCH_CHECK();
   return hipSuccess;
 }

@@ -11,7 +11,9 @@ Additions (new flags only; no reference flag changes meaning):
 ``--grad_semantics {ref,exact}`` (Q2), ``--dist_backend``, ``--seed``, ``--head``,
 ``--feat_dim`` (Q11), ``--resume``, ``--cuda_graph``, ``--work_dir``,
 ``--knn_freq`` / ``--knn`` with ``--knn_k`` / ``--knn_t`` (weighted k-NN monitor, engine/knn.py),
-``--blur_p`` / ``--blur_kernel`` / ``--blur_sigma`` (Gaussian-blur augmentation, data/augment.py).
+``--blur_p`` / ``--blur_kernel`` / ``--blur_sigma`` (Gaussian-blur augmentation, data/augment.py),
+``--val_folder`` / ``--resize`` (ImageFolder evaluation: Resize + CenterCrop on the GPU; the linear
+probe also takes ``--dataset path`` with ``--size`` / ``--mean`` / ``--std``).
 Fixes: ``--num_workers`` is honoured (Q6): it sizes the image-decode thread pool of
 ``dataset=path`` and the CPU augmentation threads of ``--gpu_aug 0`` (the default pipeline
 is the GPU kernel, which needs no workers); ``dataset=path`` parses ``--mean/--std``
@@ -90,6 +92,36 @@ def _add_common_new_flags(p: argparse.ArgumentParser):
                    help="per-phase HIP-event timings in the log + ROCTX ranges for rocprofv3 --marker-trace")
 
 
+def _add_eval_flags(g):
+    g.add_argument("--val_folder", type=str, default=None,
+                   help="ImageFolder of the validation split of --dataset path (same class sub-directories "
+                        "as --data_folder)")
+    g.add_argument("--resize", type=int, default=0,
+                   help="evaluation Resize target of the shorter side before CenterCrop(--size) "
+                        "(0 = size / 0.875 rounded: 256 for 224)")
+
+
+def list_classes(root: str) -> List[str]:
+    """Sorted class sub-directory names of an ImageFolder."""
+    return sorted(d for d in os.listdir(root) if os.path.isdir(os.path.join(root, d)))
+
+
+def _check_val_folder(opt):
+    """--val_folder and --resize of a ``path`` dataset; the two folders must hold the same classes."""
+    if opt.resize < 0 or (opt.resize and opt.resize < opt.size) or opt.resize > 32768:
+        raise ValueError(f"--resize {opt.resize} must be 0 (automatic) or in [--size, 32768]")
+    if opt.val_folder is None or opt.synthetic:
+        return
+    for f in (opt.data_folder, opt.val_folder):
+        if not os.path.isdir(f):
+            raise ValueError(f"{f!r} is not a directory")
+    tr, va = list_classes(opt.data_folder), list_classes(opt.val_folder)
+    if tr != va:
+        diff = sorted(set(tr) ^ set(va))
+        raise ValueError(f"--val_folder has other classes than --data_folder ({len(va)} vs {len(tr)}; "
+                         f"differing: {diff[:5]}{' ...' if len(diff) > 5 else ''})")
+
+
 def _add_knn_flags(g):
     g.add_argument("--knn_k", type=int, default=200, help="neighbours of the weighted k-NN evaluation")
     g.add_argument("--knn_t", type=float, default=0.1, help="temperature of the k-NN vote exp(sim/T)")
@@ -157,6 +189,7 @@ def pretrain_parser() -> argparse.ArgumentParser:
                    help="blur kernel size, odd (0 = 10%% of --size, made odd, at least 3)")
     g.add_argument("--blur_sigma", type=float, nargs=2, default=[0.1, 2.0], metavar=("LO", "HI"),
                    help="blur sigma is drawn uniformly from [LO, HI]")
+    _add_eval_flags(g)
     _add_common_new_flags(p)
     return p
 
@@ -198,9 +231,11 @@ def parse_pretrain(argv: Optional[Sequence[str]] = None, make_dirs: bool = True,
         assert opt.data_folder is not None and opt.mean is not None and opt.std is not None
     if opt.knn_freq < 0 or opt.knn_k < 1 or not opt.knn_t > 0:
         raise ValueError("--knn_freq >= 0, --knn_k >= 1 and --knn_t > 0 are required")
-    if opt.knn_freq > 0 and opt.dataset == "path":
+    if opt.knn_freq > 0 and opt.dataset == "path" and opt.val_folder is None:
         raise ValueError("--knn_freq needs a dataset with a validation split (cifar10, cifar100 or --synthetic); "
-                         "--dataset path has none")
+                         "--dataset path has none unless --val_folder names one")
+    if opt.dataset == "path":
+        _check_val_folder(opt)
     opt.blur_sigma = tuple(opt.blur_sigma)
     if not 0.0 <= opt.blur_p <= 1.0 or opt.blur_kernel < 0 or not 0.0 < opt.blur_sigma[0] <= opt.blur_sigma[1]:
         raise ValueError("--blur_p in [0, 1], --blur_kernel >= 0 and --blur_sigma 0 < LO <= HI are required")
@@ -262,7 +297,7 @@ def linear_parser() -> argparse.ArgumentParser:
     p.add_argument("--weight_decay", type=float, default=0, help="weight decay")
     p.add_argument("--momentum", type=float, default=0.9, help="momentum")
     p.add_argument("--model", type=str, default="resnet50")
-    p.add_argument("--dataset", type=str, default="cifar10", choices=["cifar10", "cifar100"])
+    p.add_argument("--dataset", type=str, default="cifar10", choices=["cifar10", "cifar100", "path"])
     p.add_argument("--cosine", action="store_true", help="using cosine annealing")
     p.add_argument("--warm", action="store_true", help="warm-up for large batch training")
     p.add_argument("--ckpt", type=str, default="", help="path to pre-trained model")
@@ -273,6 +308,10 @@ def linear_parser() -> argparse.ArgumentParser:
     g.add_argument("--knn", action="store_true",
                    help="report the loaded checkpoint's weighted k-NN accuracy before classifier training")
     _add_knn_flags(g)
+    g.add_argument("--size", type=int, default=32, help="input size (CenterCrop / RandomResizedCrop)")
+    g.add_argument("--mean", type=str, help="mean of dataset in path in form of str tuple")
+    g.add_argument("--std", type=str, help="std of dataset in path in form of str tuple")
+    _add_eval_flags(g)
     _add_common_new_flags(p)
     return p
 
@@ -282,6 +321,14 @@ def parse_linear(argv: Optional[Sequence[str]] = None, make_dirs: bool = True,
     opt = linear_parser().parse_args(argv)
     if opt.knn_k < 1 or not opt.knn_t > 0:
         raise ValueError("--knn_k >= 1 and --knn_t > 0 are required")
+    if opt.size < 1:
+        raise ValueError("--size >= 1 is required")
+    if opt.dataset == "path":
+        if opt.mean is None or opt.std is None:
+            raise ValueError("--dataset path needs --mean and --std")
+        if opt.val_folder is None and not opt.synthetic:
+            raise ValueError("--dataset path needs --val_folder (the validation ImageFolder) or --synthetic")
+        _check_val_folder(opt)
     rank, local_rank, world = env_rank_info(opt.local_rank)
     opt.rank, opt.local_rank, opt.world_size = rank, local_rank, world
     _finish_common(opt, True)
@@ -290,7 +337,8 @@ def parse_linear(argv: Optional[Sequence[str]] = None, make_dirs: bool = True,
     if opt.cosine:
         opt.model_name = f"{opt.model_name}_cosine"
     _warm_fields(opt)
-    opt.n_cls = N_CLASSES[opt.dataset]
+    # path: the class count comes from the dataset at engine start
+    opt.n_cls = N_CLASSES.get(opt.dataset, 0)
     now = now or datetime.datetime.now()
     conf_work_path = "classifier_" + now.strftime("%m%d_%H%M") + "_"
     opt.conf_work_path = conf_work_path
@@ -304,5 +352,8 @@ def parse_linear(argv: Optional[Sequence[str]] = None, make_dirs: bool = True,
             opt.tb_folder = unique_dir(opt.tb_folder)
         os.makedirs(opt.tb_folder, exist_ok=True)
         os.makedirs(opt.save_folder, exist_ok=True)
-    opt.mean_t, opt.std_t = DATASET_STATS[opt.dataset]
+    if opt.dataset == "path":
+        opt.mean_t, opt.std_t = parse_tuple(opt.mean), parse_tuple(opt.std)
+    else:
+        opt.mean_t, opt.std_t = DATASET_STATS[opt.dataset]
     return opt

@@ -100,8 +100,19 @@ class AugConfig:
     blur_p: float = 0.0
     blur_kernel: int = 0          # 0 = automatic: 10 % of the side, odd, at least 3
     blur_sigma: Sequence[float] = (0.1, 2.0)
+    # evaluation transform Resize(resize) on the shorter side + CenterCrop(size) + normalize
+    # (:meth:`center_crop`); 0 = off
+    resize: int = 0
 
     def __post_init__(self):
+        if self.resize:
+            if self.resize < 0 or not 1 <= self.size <= self.resize <= 32768:
+                raise ValueError(f"resize {self.resize} must be in [size, 32768] = [{self.size}, 32768]")
+            if self.n_views != 1:
+                raise ValueError(f"resize + centre crop makes one view, not n_views = {self.n_views}")
+            if self.crop or self.flip or self.jitter_p > 0 or self.gray_p > 0 or self.blur_p > 0:
+                raise ValueError("resize + centre crop takes no random stage: crop, flip, jitter_p, gray_p and "
+                                 "blur_p must be off")
         if self.blur_p == 0:
             return
         if not 0.0 < self.blur_p <= 1.0:
@@ -138,6 +149,19 @@ class AugConfig:
         return AugConfig(size=size, n_views=1, jitter_p=0.0, brightness=0, contrast=0, saturation=0, hue=0,
                          gray_p=0.0, crop=False, flip=False, mean=mean, std=std)
 
+    @staticmethod
+    def center_crop(size, mean, std, resize=0):
+        """torchvision's evaluation transform Resize(resize) + CenterCrop(size) + normalize;
+        ``resize`` 0 = size / 0.875 rounded (256 for 224)."""
+        return AugConfig(size=size, n_views=1, jitter_p=0.0, brightness=0, contrast=0, saturation=0, hue=0,
+                         gray_p=0.0, crop=False, flip=False, mean=mean, std=std,
+                         resize=resize or default_resize(size))
+
+
+def default_resize(size: int) -> int:
+    """The Resize target of a centre crop of ``size``: size / 0.875 rounded (224 -> 256, 32 -> 37)."""
+    return (16 * size + 7) // 14
+
 
 def gpu_augment(data: torch.Tensor, idx: torch.Tensor, cfg: AugConfig, seed, seed_t=None, offs=None,
                 hw=None, _blur_rows: int = 0) -> torch.Tensor:
@@ -146,8 +170,12 @@ def gpu_augment(data: torch.Tensor, idx: torch.Tensor, cfg: AugConfig, seed, see
     offsets, int32 [N, 2] sizes; data/datasets.py load_image_folder).
     ``cfg.blur_p > 0`` runs the kernel with the blur stage. ``_blur_rows`` is not part of the
     interface: rows per barrier round (0 = the plan's choice), for tools/aug_blur_bench.py and the
-    tests only; it schedules the stream through LDS and never changes the output."""
+    tests only; it schedules the stream through LDS and never changes the output.
+    ``cfg.resize > 0`` runs the evaluation transform (Resize + CenterCrop + normalize): no draws,
+    ``seed`` is unused."""
     m = _ext.require()
+    if cfg.resize > 0:
+        return m.gpu_eval_crop(data, idx, cfg.size, cfg.resize, list(cfg.mean), list(cfg.std), offs, hw)
     if cfg.blur_p > 0:
         return m.gpu_augment_blur(data, idx, cfg.size, cfg.n_views, int(seed) & ((1 << 63) - 1), list(cfg.mean),
                                   list(cfg.std), cfg.scale[0], cfg.scale[1], cfg.ratio[0], cfg.ratio[1],
@@ -252,13 +280,68 @@ def _hue(img, hf):
     return torch.stack([rr.gather(0, sel)[0], gg.gather(0, sel)[0], bb.gather(0, sel)[0]])
 
 
+def resized_hw(H: int, W: int, resize: int):
+    """Size of Resize(resize): the shorter side becomes ``resize``, the longer floor(resize·long/short)."""
+    lng = (resize * max(H, W)) // min(H, W)
+    return (resize, lng) if H <= W else (lng, resize)
+
+
+def center_crop_offset(d: int) -> int:
+    """torchvision's CenterCrop offset int(round(d / 2.0)): half to even."""
+    t = d // 2
+    return t + 1 if d % 2 and t % 2 else t
+
+
+def _resize_taps(n_in: int, n_out: int, first: int, count: int) -> torch.Tensor:
+    """fp32 [count, n_in] weights of outputs first..first+count-1 of the antialiased bilinear
+    resize n_in -> n_out (the triangle filter of F.interpolate(antialias=True)). Window bounds
+    and tap offsets are exact integers over 2·n_out, as in aug.hip eval_crop_kernel."""
+    sup = max(n_in, n_out)
+    i = torch.arange(first, first + count, dtype=torch.int64).unsqueeze(1)
+    j = torch.arange(n_in, dtype=torch.int64).unsqueeze(0)
+    a = (2 * i + 1) * n_in + n_out
+    lo = torch.clamp((a - 2 * sup).div(2 * n_out, rounding_mode="floor"), min=0)
+    hi = torch.clamp((a + 2 * sup).div(2 * n_out, rounding_mode="floor"), max=n_in)
+    num = 2 * j * n_out + n_out - (2 * i + 1) * n_in
+    k = torch.tensor(0.5, dtype=torch.float32) / torch.tensor(float(sup), dtype=torch.float32)
+    w = (1.0 - num.abs().float() * k).clamp_(min=0.0)
+    w = torch.where((j >= lo) & (j < hi), w, torch.zeros_like(w))
+    return w / w.sum(1, keepdim=True)
+
+
+def _center_crop_reference(data, idx, cfg: AugConfig, offs, hw) -> torch.Tensor:
+    """The fp32 CPU twin of aug.hip eval_crop_kernel."""
+    B, S, R = idx.shape[0], cfg.size, cfg.resize
+    out = torch.zeros(B, S, S, 8)
+    mean_t, std_t = torch.tensor(cfg.mean).view(1, 1, 3), torch.tensor(cfg.std).view(1, 1, 3)
+    for b in range(B):
+        src = int(idx[b])
+        if offs is None:
+            H, W = data.shape[1], data.shape[2]
+            img = data[src].float()
+        else:
+            H, W = int(hw[src, 0]), int(hw[src, 1])
+            o = int(offs[src])
+            img = data[o:o + H * W * 3].view(H, W, 3).float()
+        oh, ow = resized_hw(H, W, R)
+        wy = _resize_taps(H, oh, center_crop_offset(oh - S), S)      # [S, H]
+        wx = _resize_taps(W, ow, center_crop_offset(ow - S), S)      # [S, W]
+        c = torch.einsum("yh,hwc->ywc", wy, img)
+        c = torch.einsum("xw,ywc->yxc", wx, c) / 255.0
+        out[b, :, :, :3] = (c - mean_t) / std_t
+    return out
+
+
 def augment_reference(data: torch.Tensor, idx: torch.Tensor, cfg: AugConfig, seed: int, offs=None,
                       hw=None) -> torch.Tensor:
-    """CPU torch implementation with identical draws; returns NHWC float [V*B, S, S, 8]."""
+    """CPU torch implementation with identical draws; returns NHWC float [V*B, S, S, 8].
+    ``cfg.resize > 0``: the evaluation transform (no draws), [B, S, S, 8]."""
     data = data.cpu()
     idx = idx.cpu()
     if offs is not None:
         offs, hw = offs.cpu(), hw.cpu()
+    if cfg.resize > 0:
+        return _center_crop_reference(data, idx, cfg, offs, hw)
     B = idx.shape[0]
     S = cfg.size
     seed = int(seed) & ((1 << 63) - 1)

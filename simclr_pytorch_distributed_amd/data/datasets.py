@@ -29,6 +29,8 @@ class ArrayDataset:
     # with (h, w) = sizes[i] (int64 [N] / int32 [N, 2]); None for a dense store
     offsets: Optional[np.ndarray] = None
     sizes: Optional[np.ndarray] = None
+    # ImageFolder: the sorted class sub-directory names (label i = classes[i]); None otherwise
+    classes: Optional[list] = None
 
     def __len__(self):
         return int(self.labels.shape[0])
@@ -214,7 +216,7 @@ def load_image_folder(root: str, size: Optional[int] = None, workers: int = 1, m
             out[i] = decode(files[i], (s, s))
         with ThreadPoolExecutor(max_workers=nw) as ex:
             list(ex.map(fill, range(len(files))))
-        return ArrayDataset(out, labels, len(classes), name)
+        return ArrayDataset(out, labels, len(classes), name, classes=classes)
 
     if size is not None:
         return dense(size)
@@ -245,14 +247,22 @@ def load_image_folder(root: str, size: Optional[int] = None, workers: int = 1, m
         flat[o:o + h * w * 3] = decode(files[i], (h, w)).reshape(-1)
     with ThreadPoolExecutor(max_workers=nw) as ex:
         list(ex.map(fill_ragged, range(len(files))))
-    return ArrayDataset(flat, labels, len(classes), name, offsets=offsets, sizes=sizes)
+    return ArrayDataset(flat, labels, len(classes), name, offsets=offsets, sizes=sizes, classes=classes)
 
 
 def build_dataset(dataset: str, data_folder: str, train: bool = True, synthetic: bool = False,
                   synthetic_size: int = 50000, size: int = 32, seed: int = 0, native: bool = False,
-                  workers: int = 1) -> ArrayDataset:
+                  workers: int = 1, eval_resize: int = 0) -> ArrayDataset:
     """``native``: an ImageFolder (``dataset='path'``) keeps native resolutions (ragged
-    store) for RandomResizedCrop; otherwise it is resized to ``size``."""
+    store) for RandomResizedCrop; otherwise it is resized to ``size``.
+
+    ``eval_resize`` = R > 0: the ImageFolder is an evaluation split for the GPU transform
+    Resize(R) + CenterCrop(``size``) (data/augment.py AugConfig.center_crop): a ragged store with
+    the shorter side capped at R, aspect kept, so a 50k-image validation store stays near 11 GB
+    instead of five times that. For an image whose shorter side was above R the GPU resample is
+    then the identity and only the crop remains; the reduction to R was done here at load time by
+    PIL's own antialiased bilinear resize (uint8 result, longer side rounded to nearest), not by
+    the GPU filter. Smaller images are stored as they are and resized on the GPU."""
     if synthetic:
         ncls = {"cifar10": 10, "cifar100": 100}.get(dataset, 10)
         n = synthetic_size if train else max(1000, synthetic_size // 5)
@@ -260,6 +270,8 @@ def build_dataset(dataset: str, data_folder: str, train: bool = True, synthetic:
     if dataset in _CIFAR:
         return load_cifar(dataset, data_folder, train)
     if dataset == "path":
+        if eval_resize > 0:
+            return load_image_folder(data_folder, None, workers, max_side=eval_resize, dense_size=size)
         if native:
             return load_image_folder(data_folder, None, workers, max_side=ragged_side_cap(size), dense_size=size)
         return load_image_folder(data_folder, size, workers)

@@ -10,6 +10,10 @@ as before it.
 Several ranks: every rank encodes a contiguous 1/W slice of the bank and of the queries (the
 last slices padded to equal length by repeating the final image; pad rows are dropped by
 index after the gather), the bank features are all-gathered, the hit counts summed.
+
+ImageFolder runs (``resize > 0``): either store may be ragged (flat bytes + ``offs``/``hw``), and
+every image goes through Resize(resize) + CenterCrop(size) on the GPU (AugConfig.center_crop), so
+the bank is the training store as it is resident for pretraining; no cropped copy is made.
 """
 from __future__ import annotations
 
@@ -26,13 +30,21 @@ from ..parallel import comm
 class KnnEvaluator:
     def __init__(self, model: torch.nn.Module, backend: str, precision: str, bank_x: torch.Tensor,
                  bank_y: torch.Tensor, val_x: torch.Tensor, val_y: torch.Tensor, mean, std, size: int, n_cls: int,
-                 k: int = 200, T: float = 0.1, batch_size: int = 512, runner=None):
+                 k: int = 200, T: float = 0.1, batch_size: int = 512, runner=None, *, bank_offs=None, bank_hw=None,
+                 val_offs=None, val_hw=None, resize: int = 0):
         self.model = model
         self.backend = backend
         self.precision = precision
         self.bank_x, self.bank_y = bank_x, bank_y.long()
         self.val_x, self.val_y = val_x, val_y.long()
-        self.aug = AugConfig.evaluation(size, mean, std)
+        if (bank_offs is None) != (bank_hw is None) or (val_offs is None) != (val_hw is None):
+            raise ValueError("offs and hw of a ragged store must be given together")
+        if resize <= 0 and (bank_offs is not None or val_offs is not None):
+            raise ValueError("a ragged store needs resize > 0 (Resize + CenterCrop)")
+        # store tensor -> its (offs, hw), (None, None) for a dense one
+        self._ragged = {id(self.bank_x): (bank_offs, bank_hw), id(self.val_x): (val_offs, val_hw)}
+        self.aug = (AugConfig.center_crop(size, mean, std, resize) if resize > 0
+                    else AugConfig.evaluation(size, mean, std))
         self.n_cls = int(n_cls)
         self.k = int(k)
         self.T = float(T)
@@ -45,14 +57,20 @@ class KnnEvaluator:
 
     # --------------------------------------------------------------------------------
     @torch.no_grad()
+    def _count(self, images: torch.Tensor) -> int:
+        """Images in a store: by index, not by the (flat, when ragged) tensor's first dimension."""
+        offs = self._ragged.get(id(images), (None, None))[0]
+        return int(offs.shape[0]) if offs is not None else int(images.shape[0])
+
     def _encode_range(self, images: torch.Tensor, lo: int, hi: int, encode) -> torch.Tensor:
-        """Features of images[lo:hi] (indices >= len(images) repeat the last image)."""
-        n = images.shape[0]
+        """Features of images lo..hi-1 (indices >= the image count repeat the last image)."""
+        n = self._count(images)
+        offs, hw = self._ragged.get(id(images), (None, None))
         dev = images.device
         outs = []
         for s in range(lo, hi, self.batch_size):
             idx = torch.arange(s, min(s + self.batch_size, hi), device=dev).clamp_(max=n - 1)
-            x = augment(images, idx, self.aug, 0)
+            x = augment(images, idx, self.aug, 0, offs, hw)
             outs.append(F.normalize(encode(x).float(), dim=1))
         return torch.cat(outs) if outs else torch.zeros((0, 0), device=dev)
 
@@ -78,7 +96,7 @@ class KnnEvaluator:
         """L2-normalised fp32 encoder features (not the projection head's) of ``images[lo:hi]``."""
         encode, restore = self._encoder_fn()
         try:
-            return self._encode_range(images, lo, images.shape[0] if hi is None else hi, encode)
+            return self._encode_range(images, lo, self._count(images) if hi is None else hi, encode)
         finally:
             restore()
 
@@ -86,7 +104,7 @@ class KnnEvaluator:
     def evaluate(self) -> Tuple[float, float]:
         """(top-1, top-5) of the validation set in percent; identical on every rank."""
         W, r = comm.world_size(), comm.rank()
-        nb, nv = self.bank_x.shape[0], self.val_x.shape[0]
+        nb, nv = self._count(self.bank_x), self._count(self.val_x)
         per_b, per_v = (nb + W - 1) // W, (nv + W - 1) // W
         encode, restore = self._encoder_fn()
         try:

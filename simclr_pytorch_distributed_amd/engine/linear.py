@@ -23,7 +23,7 @@ from typing import Optional
 import torch
 import torch.nn.functional as F
 
-from ..data.augment import AugConfig, augment, nhwc8_to_nchw
+from ..data.augment import AugConfig, augment, default_resize, nhwc8_to_nchw
 from ..data.datasets import build_dataset
 from ..data.sampler import DistributedIndexSampler
 from ..models.executor import ModelRunner
@@ -62,6 +62,33 @@ class LinearEngine:
             p.requires_grad_(False)
         self.model = model
         self.runner = ModelRunner(model, self.backend, opt.precision)
+        nw = getattr(opt, "num_workers", 1)
+        size = getattr(opt, "size", 32)
+        # a real ImageFolder: native-resolution ragged training store (RandomResizedCrop on the
+        # original pixels), validation store capped at the Resize target, Resize + CenterCrop on
+        # the GPU; CIFAR and --synthetic: dense stores, normalize only
+        folder = opt.dataset == "path" and not opt.synthetic
+        self.resize = (getattr(opt, "resize", 0) or default_resize(size)) if folder else 0
+        tr = build_dataset(opt.dataset, opt.data_folder, True, opt.synthetic, opt.synthetic_size, size, opt.seed,
+                           native=folder, workers=nw)
+        va = build_dataset(opt.dataset, opt.val_folder if folder else opt.data_folder, False, opt.synthetic,
+                           opt.synthetic_size, size, opt.seed, workers=nw, eval_resize=self.resize)
+        if folder and tr.classes != va.classes:
+            raise ValueError("--val_folder has other classes than --data_folder")
+        if not opt.n_cls:
+            opt.n_cls = max(tr.num_classes, va.num_classes)
+        self.tr_x, self.tr_y = torch.from_numpy(tr.images).to(dev), torch.from_numpy(tr.labels).to(dev)
+        self.va_x, self.va_y = torch.from_numpy(va.images).to(dev), torch.from_numpy(va.labels).to(dev)
+        self.tr_offs = torch.from_numpy(tr.offsets).to(dev) if tr.ragged else None
+        self.tr_hw = torch.from_numpy(tr.sizes).to(dev) if tr.ragged else None
+        self.va_offs = torch.from_numpy(va.offsets).to(dev) if va.ragged else None
+        self.va_hw = torch.from_numpy(va.sizes).to(dev) if va.ragged else None
+        self.n_val = len(va)
+        # the reference DataLoader keeps the last partial batch (main_ce.py set_loader)
+        self.sampler = DistributedIndexSampler(len(tr), opt.batch_size, 1, 0, seed=opt.seed, drop_last=False)
+        self.aug_train = AugConfig.linear_train(size, opt.mean_t, opt.std_t)
+        self.aug_val = (AugConfig.center_crop(size, opt.mean_t, opt.std_t, self.resize) if folder
+                        else AugConfig.evaluation(size, opt.mean_t, opt.std_t))
         self.classifier = LinearClassifier(opt.model, opt.n_cls).to(dev)
         self.folded = None
         self.native_ce = None
@@ -73,17 +100,6 @@ class LinearEngine:
         self.criterion = torch.nn.CrossEntropyLoss()
         self.optimizer = torch.optim.SGD(self.classifier.parameters(), lr=opt.learning_rate, momentum=opt.momentum,
                                          weight_decay=opt.weight_decay)
-        nw = getattr(opt, "num_workers", 1)
-        tr = build_dataset(opt.dataset, opt.data_folder, True, opt.synthetic, opt.synthetic_size, 32, opt.seed,
-                           workers=nw)
-        va = build_dataset(opt.dataset, opt.data_folder, False, opt.synthetic, opt.synthetic_size, 32, opt.seed,
-                           workers=nw)
-        self.tr_x, self.tr_y = torch.from_numpy(tr.images).to(dev), torch.from_numpy(tr.labels).to(dev)
-        self.va_x, self.va_y = torch.from_numpy(va.images).to(dev), torch.from_numpy(va.labels).to(dev)
-        # the reference DataLoader keeps the last partial batch (main_ce.py set_loader)
-        self.sampler = DistributedIndexSampler(len(tr), opt.batch_size, 1, 0, seed=opt.seed, drop_last=False)
-        self.aug_train = AugConfig.linear_train(32, opt.mean_t, opt.std_t)
-        self.aug_val = AugConfig.evaluation(32, opt.mean_t, opt.std_t)
         from ..utils.tb import Logger
         self.logger = Logger(opt.tb_folder, flush_secs=2)
         self.prof = PhaseTimer(getattr(opt, "profile", False), dev)
@@ -132,7 +148,8 @@ class LinearEngine:
             dtm.update(time.time() - end)
             ph = self.prof.phase
             with ph("augment"):
-                x = augment(self.tr_x, idx, self.aug_train, step_seed(opt.seed, epoch, idx_i, 0))
+                x = augment(self.tr_x, idx, self.aug_train, step_seed(opt.seed, epoch, idx_i, 0), self.tr_offs,
+                            self.tr_hw)
                 labels = self.tr_y[idx]
             bsz = labels.shape[0]
             warmup_learning_rate(opt, epoch, idx_i, iters, self.optimizer)
@@ -165,12 +182,12 @@ class LinearEngine:
     def validate(self):
         opt = self.opt
         self.classifier.eval()
-        n = self.va_x.shape[0]
+        n = self.n_val
         losses, top1, top5 = AverageMeter(), AverageMeter(), AverageMeter()
         vb = opt.val_batch_size
         for i, s in enumerate(range(0, n, vb)):
             idx = torch.arange(s, min(s + vb, n), device=self.device)
-            x = augment(self.va_x, idx, self.aug_val, 0)
+            x = augment(self.va_x, idx, self.aug_val, 0, self.va_offs, self.va_hw)
             labels = self.va_y[idx]
             output, loss, acc1, acc5 = self._classify(self._features(x), labels, False)
             bsz = labels.shape[0]
@@ -190,8 +207,9 @@ class LinearEngine:
         opt = self.opt
         t0 = time.time()
         ev = KnnEvaluator(self.model, self.backend, opt.precision, self.tr_x, self.tr_y, self.va_x, self.va_y,
-                          opt.mean_t, opt.std_t, 32, opt.n_cls, opt.knn_k, opt.knn_t,
-                          runner=self.runner if self.backend != "native" else None)
+                          opt.mean_t, opt.std_t, getattr(opt, "size", 32), opt.n_cls, opt.knn_k, opt.knn_t,
+                          runner=self.runner if self.backend != "native" else None, bank_offs=self.tr_offs,
+                          bank_hw=self.tr_hw, val_offs=self.va_offs, val_hw=self.va_hw, resize=self.resize)
         acc1, acc5 = ev.evaluate()
         logging.info("kNN: epoch {} Acc@1 {:.2f} Acc@5 {:.2f} ({:.2f}s)".format(0, acc1, acc5, time.time() - t0))
         self.logger.log_value("knn/val_acc1", acc1, 0)

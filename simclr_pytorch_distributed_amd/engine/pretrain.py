@@ -193,18 +193,30 @@ class PretrainEngine:
 
     def _build_knn(self, train_ds):
         """The weighted k-NN monitor (--knn_freq): bank = the training images already resident
-        on the device, queries = the validation split, loaded here once."""
+        on the device, queries = the validation split, loaded here once. An ImageFolder's
+        native-resolution ragged store is the bank in place (Resize + CenterCrop on the GPU at
+        every evaluation, no second copy); its queries are --val_folder."""
+        from ..data.augment import default_resize
         from .knn import KnnEvaluator
         opt = self.opt
-        if train_ds.ragged:
-            raise ValueError("--knn_freq needs a fixed-size dataset with a validation split")
-        va = build_dataset(opt.dataset, opt.data_folder, False, opt.synthetic, opt.synthetic_size, opt.size, opt.seed,
-                           workers=opt.num_workers)
-        n_cls = opt.n_cls or int(max(int(train_ds.labels.max()), int(va.labels.max()))) + 1
+        val_folder = getattr(opt, "val_folder", None)
+        if train_ds.ragged and not val_folder:
+            raise ValueError("--knn_freq needs a fixed-size dataset with a validation split, or --val_folder")
+        resize = (getattr(opt, "resize", 0) or default_resize(opt.size)) if train_ds.ragged else 0
+        va = build_dataset(opt.dataset, val_folder if train_ds.ragged else opt.data_folder, False, opt.synthetic,
+                           opt.synthetic_size, opt.size, opt.seed, workers=opt.num_workers, eval_resize=resize)
+        if train_ds.ragged and train_ds.classes != va.classes:
+            raise ValueError("--val_folder has other classes than --data_folder")
+        n_cls = opt.n_cls or (max(train_ds.num_classes, va.num_classes) if train_ds.ragged else
+                              int(max(int(train_ds.labels.max()), int(va.labels.max()))) + 1)
+        dev = self.device
         return KnnEvaluator(self.model, self.backend, opt.precision, self.data, self.labels,
-                            torch.from_numpy(va.images).to(self.device), torch.from_numpy(va.labels).to(self.device),
+                            torch.from_numpy(va.images).to(dev), torch.from_numpy(va.labels).to(dev),
                             opt.mean_t, opt.std_t, opt.size, n_cls, opt.knn_k, opt.knn_t,
-                            runner=self.runner if self.backend != "native" else None)
+                            runner=self.runner if self.backend != "native" else None,
+                            bank_offs=self.data_offs, bank_hw=self.data_hw,
+                            val_offs=torch.from_numpy(va.offsets).to(dev) if va.ragged else None,
+                            val_hw=torch.from_numpy(va.sizes).to(dev) if va.ragged else None, resize=resize)
 
     def knn_eval(self, epoch: int):
         """Run the k-NN monitor, log it and (rank 0) write knn/val_acc1, knn/val_acc5."""
