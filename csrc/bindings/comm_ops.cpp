@@ -3,7 +3,7 @@
 // The reference's SyncBN (main_supcon.py:222-224 -> torch.nn.SyncBatchNorm) issues one
 // all-gather per BN in forward and one all-reduce in backward, each a Python-level c10d
 // call (≈106 per ResNet-50 step, all on the critical path). Here a "small communicator"
-// is a handle the executor (conv_bn_ops.cpp block_fwd / block_bwd) calls directly on the
+// is a handle the executor (block_ops.cpp block_fwd / block_bwd) calls directly on the
 // compute stream, with no Python or c10d work queue in between:
 //
 //   kind RCCL  — a dedicated RCCL communicator (ncclCommInitRankConfig from a unique id

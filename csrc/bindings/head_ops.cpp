@@ -29,8 +29,6 @@
 hipError_t launch_cast_f32_bf16(const float* x, void* y, long n, hipStream_t s);
 
 namespace sdx_bind {
-std::vector<torch::Tensor>& side_stash();   // conv_bn_ops.cpp: released at the side-stream join
-
 namespace {
 
 void check_w(const torch::Tensor& w, int64_t rows, int64_t cols, const char* name) {
@@ -64,10 +62,7 @@ int head_cfg(int64_t rows, int64_t ncol, int64_t kdim) {
 
 ConvGeom gemm_geom(int64_t rows, int64_t in, int64_t out) {
   // a [rows] x [in] -> [out] GEMM as a 1x1 conv over `rows` single-pixel images
-  ConvGeom g{};
-  g.N = (int)rows; g.H = g.W = 1; g.C = (int)in; g.K = (int)out;
-  g.R = g.S = 1; g.P = g.Q = 1; g.stride = 1; g.pad = 0;
-  return g;
+  return conv_geom(rows, 1, 1, in, out, 1, 1, 1, 0);
 }
 
 // y[rows][out] = x[rows][in] · W[out][in]ᵀ (+ bias) (ReLU); bf16 or fp32 output
@@ -155,29 +150,6 @@ torch::Tensor gemm_dgrad(const torch::Tensor& dy, const torch::Tensor& wt, int64
   return dx;
 }
 
-// the head's side-stream fork: everything queued on the compute stream so far, then `keep`
-// stays alive until the side stream is joined (side_stash). Own small event pool: two forks
-// per step; no system-scope fence (same-device stream ordering, conv_bn_ops.cpp next_event)
-void head_fork(hipStream_t main, hipStream_t ss, std::initializer_list<torch::Tensor> keep) {
-  static std::mutex mu;
-  static std::vector<hipEvent_t> pool;
-  static size_t next = 0;
-  hipEvent_t ev;
-  {
-    std::lock_guard<std::mutex> lk(mu);
-    if (pool.empty()) {
-      pool.resize(64);
-      for (auto& e : pool)
-        check_hip(hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventDisableSystemFence), "hipEventCreate");
-    }
-    ev = pool[next];
-    next = (next + 1) % pool.size();
-  }
-  check_hip(hipEventRecord(ev, main), "hipEventRecord");
-  check_hip(hipStreamWaitEvent(ss, ev, 0), "hipStreamWaitEvent");
-  for (const auto& t : keep) side_stash().push_back(t);
-}
-
 // feat [N][D] fp32|bf16; w1 [O1][D] bf16 (+ b1 fp32); MLP: w2 [O2][O1] bf16 (+ b2).
 // Returns [z fp32 [N][O_last], fb bf16 [N][D], h bf16 [N][O1] (MLP; empty otherwise)].
 std::vector<torch::Tensor> head_fwd(torch::Tensor feat, torch::Tensor w1, torch::Tensor b1, OptT w2, OptT b2) {
@@ -215,19 +187,17 @@ torch::Tensor head_bwd(torch::Tensor dz, torch::Tensor fb, OptT h, torch::Tensor
     TORCH_CHECK(h.has_value() && sw2.has_value() && sb2.has_value(), "MLP head: h, sw2, sb2 required");
     check_2d(*h, at::kBFloat16, "h");
     const int64_t O1 = h->size(1);
-    hipStream_t main = cur_stream(), ss = reinterpret_cast<hipStream_t>(side);
-    auto hs = c10::hip::getStreamFromExternal(ss, dz.device().index());
-    head_fork(main, ss, {dz, dzb, *h});
+    // each fork: everything queued on the compute stream so far, then the listed tensors
+    // stay alive until the side stream is joined (side_stream.cpp)
     {
-      c10::hip::HIPStreamGuard guard(hs);
+      auto guard = side_fork(side, dz.device(), {dz, dzb, *h});
       colsum_into(dz, rows, 1, O, sb_last);
       gemm_wgrad(dzb, *h, *sw2);
     }
     torch::Tensor slab1;   // the hidden bias gradient's column sums, reduced on the side stream
     auto dh = gemm_dgrad(dzb, *w2t, O1, false, &*h, &sb1, &slab1);
-    head_fork(main, ss, {dh, fb, slab1});
     {
-      c10::hip::HIPStreamGuard guard(hs);
+      auto guard = side_fork(side, dz.device(), {dh, fb, slab1});
       colsum_into(slab1, slab1.size(0), 2, O1, sb1);
       gemm_wgrad(dh, fb, sw1);
     }

@@ -3,7 +3,9 @@
 
 namespace sdx_bind {
 void register_supcon(pybind11::module& m);
-void register_conv_bn(pybind11::module& m);
+void register_conv(pybind11::module& m);
+void register_bn(pybind11::module& m);
+void register_block(pybind11::module& m);
 void register_data(pybind11::module& m);
 void register_optim(pybind11::module& m);
 void register_pool(pybind11::module& m);
@@ -16,7 +18,9 @@ void register_knn(pybind11::module& m);
 
 void register_ops(pybind11::module& m) {
   register_supcon(m);
-  register_conv_bn(m);
+  register_conv(m);
+  register_bn(m);
+  register_block(m);
   register_data(m);
   register_optim(m);
   register_pool(m);

@@ -245,7 +245,7 @@ torch::Tensor xgmi_emulate(torch::Tensor in, int64_t iters) {
 
 }  // namespace
 
-// for comm_ops.cpp / conv_bn_ops.cpp: arguments of one fused SyncBN exchange on arena id
+// for comm_ops.cpp / bn_ops.cpp: arguments of one fused SyncBN exchange on arena id
 // (epoch advanced; mode 1 real peers, 2 emulated ranks)
 XgmiCol xgmi_col_args(int64_t id) {
   Arena& a = get(id);

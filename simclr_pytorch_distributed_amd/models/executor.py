@@ -8,7 +8,7 @@ this executor walks them and issues the fused native ops instead of ``nn.Conv2d`
 * every conv (training) emits its BN statistics from the epilogue; every BN+ReLU (and
   BN+shortcut-BN+add+ReLU) is one fused elementwise pass; each residual block's forward
   and backward kernel sequence is issued by ONE C++ call (ops/block.py ->
-  csrc/bindings/conv_bn_ops.cpp block_fwd / block_bwd); SyncBN statistics are exchanged
+  csrc/bindings/block_ops.cpp block_fwd / block_bwd); SyncBN statistics are exchanged
   by the native communicator inside that call (a dedicated RCCL communicator by default; with
   ``--syncbn_comm xgmi`` the fused xGMI exchange: reduce + exchange + finalize in one launch per BN);
 * global average pooling is a native kernel (pool.hip) and the projection head one

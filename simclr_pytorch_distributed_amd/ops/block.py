@@ -321,7 +321,7 @@ class BlockChain:
 
 
 class _NativeBlock(torch.autograd.Function):
-    """Whole residual block through the native executor (csrc/bindings/conv_bn_ops.cpp
+    """Whole residual block through the native executor (csrc/bindings/block_ops.cpp
     ``block_fwd`` / ``block_bwd``): one host call per block and direction instead of
     ~12 / ~20 Python-level kernel calls. Same kernels and math as :class:`_Bottleneck` /
     :class:`_Basic` (materialised internal activations, ReLU masks from y in backward,

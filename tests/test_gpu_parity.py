@@ -558,3 +558,55 @@ def test_merged_splitk_reductions_bit_identical(gpu):
         m.splitk_merge_set(bool(prev))
     assert torch.equal(grads[0], grads[1]), "unmerged step is not deterministic"
     assert torch.equal(grads[0], grads[2])
+
+
+@pytest.mark.parametrize("first", [0, 2])
+def test_block_pairs_side_stream_bit_identical(gpu, first, monkeypatch):
+    """A pair of consecutive ResNet-50 blocks (BN3 fold on) gives dx and every parameter
+    gradient bit for bit with the side stream (shortcut conv, weight gradients and the
+    fold's Gram forked off the compute stream) and without it (``ops.streams.ENABLED``
+    False: ``side = 0`` in block_fwd, block_bwd and fold_gram, everything in line): the
+    fork only reorders launches across streams, never what a kernel computes. Pair (0, 1):
+    the stride-1 projection block, then a folding identity block; pair (2, 3): a folding
+    identity block, then the strided projection block. 8 images."""
+    from simclr_pytorch_distributed_amd.models.executor import ModelRunner
+    from simclr_pytorch_distributed_amd.ops import block as fb
+    from simclr_pytorch_distributed_amd.ops import streams
+    from simclr_pytorch_distributed_amd.optim.flat import FlatParams
+    monkeypatch.setattr(fb, "BN3_FOLD", True)
+    monkeypatch.setattr(fb, "BN3_FOLD_ROWS_PER_K2", 0.0)   # fold at this small batch too
+    monkeypatch.setattr(fb, "BN3_FOLD_MAXK", 128)
+    nat_m, ref_m = _models(gpu, "resnet50")
+    flat = FlatParams(nat_m)
+    runner = ModelRunner(nat_m, "native", master=flat.flat)
+    wc = runner.weight_cache()
+    nb, rb = list(nat_m.encoder.blocks()), list(ref_m.encoder.blocks())
+    with torch.no_grad():
+        r = torch.relu(ref_m.encoder.bn1(ref_m.encoder.conv1(_images(gpu, 8))))
+        for blk in rb[:first]:
+            r = blk(r)
+    xin = r.to(torch.bfloat16).permute(0, 2, 3, 1).contiguous()
+    dy = None
+    runs = []
+    for side_on in (True, False):
+        monkeypatch.setattr(streams, "ENABLED", side_on)
+        flat.zero_grad()
+        wc.refresh()
+        chain = fb.BlockChain()
+        xn = xin.clone().requires_grad_(True)
+        out = xn
+        for j, blk in enumerate(nb[first:first + 2]):
+            out = fb.bottleneck(out, blk, wc, True, None, chain, next_native=j == 0)
+        if dy is None:
+            dy = torch.randn(out.shape, generator=torch.Generator().manual_seed(9)).to(gpu).to(torch.bfloat16)
+        out.backward(dy)
+        streams.join(xn.device)
+        torch.cuda.synchronize()
+        grads = {"dx": xn.grad.clone()}
+        for j in (first, first + 1):
+            for n, p in nb[j].named_parameters():
+                grads[f"block {j} {n}"] = p.grad.clone()
+        runs.append(grads)
+    assert runs[0].keys() == runs[1].keys() and len(runs[0]) > 1
+    diff = [n for n in runs[0] if not torch.equal(runs[0][n], runs[1][n])]
+    assert not diff, f"side stream on / off differ in: {diff}"

@@ -3,7 +3,7 @@
 For every distinct weight-gradient GEMM, times the native split-K wgrad (kernel + slab
 reduce) for each tile config and a range of split counts, and prints the auto choice's
 time next to the best found. Used to calibrate ``conv_wgrad``'s split / tile heuristic
-(csrc/bindings/conv_bn_ops.cpp).
+(csrc/bindings/conv_ops.cpp).
 
 Usage: python tools/wgrad_sweep.py [--views 512] [--iters 20] [--cfgs 0,1,2,3,4]
 """
