@@ -1,16 +1,11 @@
 // Linear-probe classifier (linear_ce.hip): fused logits + cross-entropy + top-k hits, and
 // the gradient + SGD update, for the native linear evaluation (ops/linear_probe.py;
-// reference main_linear.py:166-244).
+// reference main_linear.py:166-244); ce_head_fwd / ce_head_bwd: the same classifier as a
+// trainable node of the supervised model (ops/ce_head.py; reference main_ce.py), whose
+// parameter gradients accumulate into the gradient sinks.
 #include "conv_internal.h"
 #include "launchers.h"
 #include "ops_decl.h"
-
-bool linear_ce_supported(int K, int C);
-hipError_t launch_linear_ce_fwd(const float* x, const float* W, const float* bias, const int64_t* labels, int B,
-                                int K, int C, float gscale, float* logits, float* dz, float* rowstat, hipStream_t s);
-hipError_t launch_linear_ce_sgd(const float* x, const float* dz, int B, int K, int C, float* W, float* bias,
-                                float* bufW, float* bufb, float lr, float mom, float wd, int first,
-                                const float* rowstat, float* stats, hipStream_t s);
 
 namespace sdx_bind {
 namespace {
@@ -20,12 +15,9 @@ void check_f32(const torch::Tensor& t, std::vector<int64_t> shape, const char* n
               " must be a contiguous fp32 GPU tensor of shape ", shape);
 }
 
-// One classifier batch. train: logits, the mean-CE gradient and the SGD update of (W, b)
-// with momentum buffers (bufW, bufb; `first` = no momentum history yet); eval: logits only.
-// Returns [logits [B][C], stats [3] = (Σ_rows CE, top-1 hits, top-5 hits)].
-std::vector<torch::Tensor> linear_ce_step(torch::Tensor x, torch::Tensor W, torch::Tensor b, torch::Tensor labels,
-                                          OptT bufW, OptT bufb, double lr, double momentum, double wd, bool first,
-                                          bool train) {
+// the shape / dtype checks shared by linear_ce_step and the ce_head ops
+void check_classifier(const torch::Tensor& x, const torch::Tensor& W, const torch::Tensor& b,
+                      const torch::Tensor& labels) {
   TORCH_CHECK(x.dim() == 2 && W.dim() == 2, "x [B][K], W [C][K]");
   const int64_t B = x.size(0), K = x.size(1), C = W.size(0);
   check_f32(x, {B, K}, "x");
@@ -33,9 +25,19 @@ std::vector<torch::Tensor> linear_ce_step(torch::Tensor x, torch::Tensor W, torc
   check_f32(b, {C}, "b");
   TORCH_CHECK(labels.is_cuda() && labels.scalar_type() == at::kLong && labels.numel() == B && labels.is_contiguous(),
               "labels: int64 [B]");
-  TORCH_CHECK(linear_ce_supported((int)K, (int)C) && ((K / 64) & (K / 64 - 1)) == 0,
+  TORCH_CHECK(B >= 1 && linear_ce_supported((int)K, (int)C) && ((K / 64) & (K / 64 - 1)) == 0,
               "linear_ce: K = 64·2^j <= 2048, C <= 1024");
   TORCH_CHECK(B * C < (1LL << 31) && B * K < (1LL << 31), "linear_ce: sizes");
+}
+
+// One classifier batch. train: logits, the mean-CE gradient and the SGD update of (W, b)
+// with momentum buffers (bufW, bufb; `first` = no momentum history yet); eval: logits only.
+// Returns [logits [B][C], stats [3] = (Σ_rows CE, top-1 hits, top-5 hits)].
+std::vector<torch::Tensor> linear_ce_step(torch::Tensor x, torch::Tensor W, torch::Tensor b, torch::Tensor labels,
+                                          OptT bufW, OptT bufb, double lr, double momentum, double wd, bool first,
+                                          bool train) {
+  check_classifier(x, W, b, labels);
+  const int64_t B = x.size(0), K = x.size(1), C = W.size(0);
   if (train) {
     TORCH_CHECK(bufW.has_value() && bufb.has_value(), "momentum buffers required for a training step");
     check_f32(*bufW, {C, K}, "bufW");
@@ -62,9 +64,82 @@ std::vector<torch::Tensor> linear_ce_step(torch::Tensor x, torch::Tensor W, torc
   return {logits, stats};
 }
 
+// Training form, forward: [logits [B][C], dz [B][C] = (softmax − onehot) / B, rowstat [B][3],
+// stats [3], loss []]. reduce: also sum the row statistics into stats / loss now (a forward
+// that no backward follows); otherwise ce_head_bwd writes them.
+std::vector<torch::Tensor> ce_head_fwd(torch::Tensor x, torch::Tensor W, torch::Tensor b, torch::Tensor labels,
+                                       bool reduce) {
+  check_classifier(x, W, b, labels);
+  const int64_t B = x.size(0), K = x.size(1), C = W.size(0);
+  c10::DeviceGuard dg(x.device());
+  auto fo = x.options();
+  auto logits = torch::empty({B, C}, fo);
+  auto dz = torch::empty({B, C}, fo);
+  auto rowstat = torch::empty({B, 3}, fo);
+  auto stats = torch::empty({3}, fo);
+  auto loss = torch::empty({}, fo);
+  check_hip(launch_linear_ce_fwd(x.data_ptr<float>(), W.data_ptr<float>(), b.data_ptr<float>(),
+                                 labels.data_ptr<int64_t>(), (int)B, (int)K, (int)C, (float)(1.0 / B),
+                                 logits.data_ptr<float>(), dz.data_ptr<float>(), rowstat.data_ptr<float>(),
+                                 cur_stream()),
+            "ce_head_fwd");
+  if (reduce)
+    check_hip(launch_ce_head_bwd(nullptr, nullptr, nullptr, (int)B, (int)K, (int)C, nullptr, nullptr, nullptr, nullptr,
+                                 rowstat.data_ptr<float>(), stats.data_ptr<float>(), loss.data_ptr<float>(),
+                                 cur_stream()),
+              "ce_head_stats");
+  return {logits, dz, rowstat, stats, loss};
+}
+
+// Training form, backward (one launch): returns dX [B][K] = gout·dz·W (need_dx), accumulates
+// dW += gout·dzᵀ·x and db += gout·Σ_b dz into the given destinations (contiguous fp32, views of
+// a larger buffer allowed) and writes stats / loss from rowstat. gout: scalar fp32 GPU tensor.
+c10::optional<torch::Tensor> ce_head_bwd(torch::Tensor x, torch::Tensor dz, torch::Tensor W, torch::Tensor gout,
+                                         torch::Tensor rowstat, torch::Tensor stats, torch::Tensor loss, OptT dW,
+                                         OptT db, bool need_dx) {
+  TORCH_CHECK(x.dim() == 2 && W.dim() == 2, "x [B][K], W [C][K]");
+  const int64_t B = x.size(0), K = x.size(1), C = W.size(0);
+  check_f32(x, {B, K}, "x");
+  check_f32(W, {C, K}, "W");
+  check_f32(dz, {B, C}, "dz");
+  check_f32(rowstat, {B, 3}, "rowstat");
+  check_f32(stats, {3}, "stats");
+  check_f32(loss, {}, "loss");
+  TORCH_CHECK(gout.is_cuda() && gout.scalar_type() == at::kFloat && gout.numel() == 1, "gout: one fp32 GPU value");
+  TORCH_CHECK(B >= 1 && linear_ce_supported((int)K, (int)C) && ((K / 64) & (K / 64 - 1)) == 0,
+              "ce_head: K = 64·2^j <= 2048, C <= 1024");
+  TORCH_CHECK(B * C < (1LL << 31) && B * K < (1LL << 31), "ce_head: sizes");
+  TORCH_CHECK(dW.has_value() == db.has_value(), "ce_head_bwd: dW and db come together");
+  if (dW.has_value()) {
+    check_f32(*dW, {C, K}, "dW");
+    check_f32(*db, {C}, "db");
+    TORCH_CHECK(dW->get_device() == x.get_device() && db->get_device() == x.get_device(), "dW / db: x's device");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(dW->data_ptr<float>()) % 16 == 0, "dW must be 16-byte aligned");
+  }
+  TORCH_CHECK(need_dx || dW.has_value(), "ce_head_bwd: nothing to compute");
+  c10::DeviceGuard dg(x.device());
+  c10::optional<torch::Tensor> dX;
+  if (need_dx) dX = torch::empty({B, K}, x.options());
+  check_hip(launch_ce_head_bwd(x.data_ptr<float>(), dz.data_ptr<float>(), W.data_ptr<float>(), (int)B, (int)K, (int)C,
+                               gout.data_ptr<float>(), need_dx ? dX->data_ptr<float>() : nullptr,
+                               dW.has_value() ? dW->data_ptr<float>() : nullptr,
+                               db.has_value() ? db->data_ptr<float>() : nullptr, rowstat.data_ptr<float>(),
+                               stats.data_ptr<float>(), loss.data_ptr<float>(), cur_stream()),
+            "ce_head_bwd");
+  return dX;
+}
+
 }  // namespace
 
 void register_probe(pybind11::module& m) {
+  m.def("ce_head_fwd", &ce_head_fwd,
+        "trainable classifier + mean cross-entropy, forward: logits, dz, row statistics (+ their sums when reduce)",
+        pybind11::arg("x"), pybind11::arg("W"), pybind11::arg("b"), pybind11::arg("labels"), pybind11::arg("reduce"));
+  m.def("ce_head_bwd", &ce_head_bwd,
+        "trainable classifier backward: dX, dW += , db += (gradient sinks), statistics; one launch",
+        pybind11::arg("x"), pybind11::arg("dz"), pybind11::arg("W"), pybind11::arg("gout"), pybind11::arg("rowstat"),
+        pybind11::arg("stats"), pybind11::arg("loss"), pybind11::arg("dW"), pybind11::arg("db"),
+        pybind11::arg("need_dx"));
   m.def("linear_ce_step", &linear_ce_step,
         "linear classifier + mean cross-entropy + top-1/5 hits (+ gradient and SGD update when train)",
         pybind11::arg("x"), pybind11::arg("W"), pybind11::arg("b"), pybind11::arg("labels"), pybind11::arg("bufW"),

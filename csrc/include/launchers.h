@@ -18,6 +18,23 @@ hipError_t launch_rownorm_bwd(const float* dy, const float* y, const float* norm
 hipError_t launch_norm_stats(const float* x, int N, int D, int mode, double* sums, double n_global, float momentum,
                              float* rec, float* valid, float* out, hipStream_t s);
 
+// ---- linear classifier + cross-entropy (linear_ce.hip) -------------------------
+// K = 64·2^j <= 2048, C <= 1024; every launcher returns hipErrorInvalidValue outside that range
+bool linear_ce_supported(int K, int C);
+// logits [B][C], dz = (softmax − onehot)·gscale (optional), rowstat [B][3] = (CE, hit@1, hit@5)
+hipError_t launch_linear_ce_fwd(const float* x, const float* W, const float* bias, const int64_t* labels, int B,
+                                int K, int C, float gscale, float* logits, float* dz, float* rowstat, hipStream_t s);
+// probe form: gradient + SGD update of (W, b) in place, stats[3] = Σ_rows rowstat
+hipError_t launch_linear_ce_sgd(const float* x, const float* dz, int B, int K, int C, float* W, float* bias,
+                                float* bufW, float* bufb, float lr, float mom, float wd, int first,
+                                const float* rowstat, float* stats, hipStream_t s);
+// training form: dX = gout·dz·W (optional), dW += gout·dzᵀ·x and db += gout·Σ_b dz (optional,
+// both or neither; 16-byte aligned), stats[3] = Σ_rows rowstat, loss = stats[0] / B.
+// gout: the upstream scalar gradient in device memory
+hipError_t launch_ce_head_bwd(const float* x, const float* dz, const float* W, int B, int K, int C, const float* gout,
+                              float* dX, float* dW, float* db, const float* rowstat, float* stats, float* loss,
+                              hipStream_t s);
+
 // ---- fused SupCon / NT-Xent loss (supcon.hip) ---------------------------------
 int supcon_num_splits(int n_own, int n_other);
 hipError_t launch_supcon_fwd(const float* A, const float* C, const int* a_self, const int* a_key,

@@ -16,6 +16,17 @@
 //                  the last block does the bias the same way and sums the per-row loss /
 //                  hit counters into stats[3] in row order.
 //
+//   ce_head_bwd    the TRAINING form's second launch (supervised CE / fine-tuning: the
+//                  classifier is part of the model, its gradients go to the flat gradient
+//                  buffer and the optimizer, the features get a gradient). Blocks take roles
+//                  by blockIdx: dX blocks (thread = 4 consecutive features of one row:
+//                  dX = gout·Σ_c dz[b][c]·W[c][k..k+3], classes in index order), dW blocks
+//                  (thread = 4 consecutive weights of one class: dW += gout·Σ_b dz[b][c]·x[b][k..k+3],
+//                  rows in index order), the last block db += gout·Σ_b dz[b][c] and the
+//                  statistics. dW / db ACCUMULATE (the gradient-sink convention); gout is the
+//                  upstream scalar gradient read from device memory. No atomics: bit-identical
+//                  from run to run.
+//
 // fp32 throughout, as the reference's classifier (its GEMMs are ~0.1 GFLOP per step: the
 // cost is launch count and latency, not FLOPs).
 #include "common.h"
@@ -158,6 +169,81 @@ __global__ __launch_bounds__(256) void linear_ce_sgd_kernel(const float* __restr
   }
 }
 
+// grid: nx = ceil(B*K/4 / 256) feature-gradient blocks (0 when dX == nullptr), then
+// nw = ceil(C*K/4 / 256) weight-gradient blocks (0 when dW == nullptr), then 1 block
+// (bias gradient + statistics). stats[3] = (Σ_rows CE, top-1 hits, top-5 hits), loss = Σ CE / B.
+__global__ __launch_bounds__(256) void ce_head_bwd_kernel(const float* __restrict__ x, const float* __restrict__ dz,
+                                                          const float* __restrict__ W, int B, int K, int C,
+                                                          const float* __restrict__ gout, int nx,
+                                                          float* __restrict__ dX, float* __restrict__ dW,
+                                                          float* __restrict__ db, const float* __restrict__ rowstat,
+                                                          float* __restrict__ stats, float* __restrict__ loss) {
+  const int k4 = K / 4;
+  if (blockIdx.x + 1 < gridDim.x) {
+    const float go = gout[0];
+    if ((int)blockIdx.x < nx) {
+      // feature gradient: one row, 4 consecutive features, classes in index order
+      const int e = blockIdx.x * 256 + threadIdx.x;
+      if (e >= B * k4) return;
+      const int b = e / k4, k = (e - b * k4) * 4;
+      const float* dr = dz + (size_t)b * C;
+      float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll 4
+      for (int c = 0; c < C; ++c) {
+        const float d = dr[c];
+        const float4 v = *reinterpret_cast<const float4*>(W + (size_t)c * K + k);
+        g.x = fmaf(d, v.x, g.x);
+        g.y = fmaf(d, v.y, g.y);
+        g.z = fmaf(d, v.z, g.z);
+        g.w = fmaf(d, v.w, g.w);
+      }
+      *reinterpret_cast<float4*>(dX + (size_t)b * K + k) =
+          make_float4(__fmul_rn(go, g.x), __fmul_rn(go, g.y), __fmul_rn(go, g.z), __fmul_rn(go, g.w));
+      return;
+    }
+    // weight gradient: one class, 4 consecutive weights, rows in index order
+    const int e = (blockIdx.x - nx) * 256 + threadIdx.x;
+    if (e >= C * k4) return;
+    const int c = e / k4, k = (e - c * k4) * 4;
+    float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll 4
+    for (int b = 0; b < B; ++b) {
+      const float d = dz[(size_t)b * C + c];
+      const float4 v = *reinterpret_cast<const float4*>(x + (size_t)b * K + k);
+      g.x = fmaf(d, v.x, g.x);
+      g.y = fmaf(d, v.y, g.y);
+      g.z = fmaf(d, v.z, g.z);
+      g.w = fmaf(d, v.w, g.w);
+    }
+    float4* wp = reinterpret_cast<float4*>(dW + (size_t)c * K + k);
+    float4 w = *wp;
+    // (the product is rounded on its own: the sum into the sink is no fused multiply-add)
+    w.x += __fmul_rn(go, g.x);
+    w.y += __fmul_rn(go, g.y);
+    w.z += __fmul_rn(go, g.z);
+    w.w += __fmul_rn(go, g.w);
+    *wp = w;
+    return;
+  }
+  // last block: bias gradient, statistics in row order
+  if (db != nullptr) {
+    const float go = gout[0];
+    for (int c = threadIdx.x; c < C; c += 256) {
+      float g = 0.f;
+      for (int b = 0; b < B; ++b) g += dz[(size_t)b * C + c];
+      db[c] += __fmul_rn(go, g);
+    }
+  }
+  if (threadIdx.x < 3) {
+    // fp64 sum (3 threads x B adds): the mean loss carries the rows' rounding only, not a
+    // B-term fp32 chain's on top of it
+    double s = 0.0;
+    for (int b = 0; b < B; ++b) s += (double)rowstat[(size_t)b * 3 + threadIdx.x];
+    stats[threadIdx.x] = (float)s;
+    if (threadIdx.x == 0) loss[0] = (float)(s / (double)B);
+  }
+}
+
 }  // namespace
 
 bool linear_ce_supported(int K, int C) { return K % 64 == 0 && K >= 64 && K <= 64 * 32 && C >= 1 && C <= kMaxClasses; }
@@ -189,6 +275,26 @@ hipError_t launch_linear_ce_sgd(const float* x, const float* dz, int B, int K, i
   const dim3 grid(W != nullptr ? (nw4 + 255) / 256 + 1 : 1), blk(256);
   hipLaunchKernelGGL(linear_ce_sgd_kernel, grid, blk, 0, s, x, dz, B, K, C, W, bias, bufW, bufb, lr, mom, wd, first,
                      rowstat, stats);
+  SDX_LAUNCH_CHECK();
+  return hipSuccess;
+}
+
+hipError_t launch_ce_head_bwd(const float* x, const float* dz, const float* W, int B, int K, int C, const float* gout,
+                              float* dX, float* dW, float* db, const float* rowstat, float* stats, float* loss,
+                              hipStream_t s) {
+  if (!linear_ce_supported(K, C) || ((K / 64) & (K / 64 - 1)) != 0 || B < 1) return hipErrorInvalidValue;
+  if ((long)B * K >= (1L << 31) || (long)B * C >= (1L << 31)) return hipErrorInvalidValue;
+  if (rowstat == nullptr || stats == nullptr || loss == nullptr) return hipErrorInvalidValue;
+  const bool grads = dX != nullptr || dW != nullptr || db != nullptr;
+  if (grads && (x == nullptr || dz == nullptr || W == nullptr || gout == nullptr)) return hipErrorInvalidValue;
+  if ((dW == nullptr) != (db == nullptr)) return hipErrorInvalidValue;
+  // the feature and weight blocks move 16 bytes per access
+  if (((uintptr_t)x | (uintptr_t)W | (uintptr_t)dX | (uintptr_t)dW) & 15) return hipErrorInvalidValue;
+  const int nx = dX != nullptr ? (B * (K / 4) + 255) / 256 : 0;
+  const int nw = dW != nullptr ? (C * (K / 4) + 255) / 256 : 0;
+  const dim3 grid(nx + nw + 1), blk(256);
+  hipLaunchKernelGGL(ce_head_bwd_kernel, grid, blk, 0, s, x, dz, W, B, K, C, gout, nx, dX, dW, db, rowstat, stats,
+                     loss);
   SDX_LAUNCH_CHECK();
   return hipSuccess;
 }

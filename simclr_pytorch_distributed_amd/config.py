@@ -4,6 +4,9 @@
   (30 flags, ``model_name`` derivation, warm-up auto-enable for ``batch_size > 256``,
   ``./work_space/{dataset}_{models,tensorboard}/{dataset}_{MMDD_HHMM}_{model_name}``).
 * :func:`linear_parser` / :func:`parse_linear` mirror main_linear.py:21-116.
+* :func:`ce_parser` / :func:`parse_ce`: supervised cross-entropy training and fine-tuning
+  (main_ce.py; the reference keeps only its loaders), with ``--ckpt``, ``--label_frac``,
+  ``--val_freq`` and ``--n_cls``.
 
 Additions (new flags only; no reference flag changes meaning):
 ``--local-rank`` (dashed alias), env rank discovery (Q13),
@@ -356,4 +359,116 @@ def parse_linear(argv: Optional[Sequence[str]] = None, make_dirs: bool = True,
         opt.mean_t, opt.std_t = parse_tuple(opt.mean), parse_tuple(opt.std)
     else:
         opt.mean_t, opt.std_t = DATASET_STATS[opt.dataset]
+    return opt
+
+
+def ce_parser() -> argparse.ArgumentParser:
+    """Supervised cross-entropy training / fine-tuning (main_ce.py). Flag names and defaults follow
+    main_linear.py (schedule) and main_supcon.py (training: --syncBN, --optimizer, --resume)."""
+    p = argparse.ArgumentParser("argument for supervised training")
+    p.add_argument("--print_freq", type=int, default=10, help="print frequency")
+    p.add_argument("--save_freq", type=int, default=50, help="save frequency")
+    p.add_argument("--batch_size", type=int, default=256, help="batch_size (global)")
+    p.add_argument("--num_workers", type=int, default=16, help="num of workers to use")
+    p.add_argument("--epochs", type=int, default=500, help="number of training epochs")
+    p.add_argument("--learning_rate", type=float, default=0.2, help="learning rate")
+    p.add_argument("--lr_decay_epochs", type=str, default="350,400,450", help="where to decay lr")
+    p.add_argument("--lr_decay_rate", type=float, default=0.1, help="decay rate for learning rate")
+    p.add_argument("--weight_decay", type=float, default=1e-4, help="weight decay")
+    p.add_argument("--momentum", type=float, default=0.9, help="momentum")
+    p.add_argument("--model", type=str, default="resnet50")
+    p.add_argument("--dataset", type=str, default="cifar10", choices=["cifar10", "cifar100", "path"])
+    p.add_argument("--mean", type=str, help="mean of dataset in path in form of str tuple")
+    p.add_argument("--std", type=str, help="std of dataset in path in form of str tuple")
+    p.add_argument("--data_folder", type=str, default=None, help="path to custom dataset")
+    p.add_argument("--size", type=int, default=32, help="parameter for RandomResizedCrop")
+    p.add_argument("--cosine", action="store_true", help="using cosine annealing")
+    p.add_argument("--syncBN", action="store_true", help="using synchronized batch normalization")
+    p.add_argument("--warm", action="store_true", help="warm-up for large batch training")
+    p.add_argument("--trial", type=str, default="0", help="id for recording multiple runs")
+    p.add_argument("--ckpt", type=str, default="",
+                   help="SupCon / SimCLR checkpoint whose encoder initialises the model (fine-tuning); "
+                        "without it the run is the supervised baseline from scratch")
+    p.add_argument("--local_rank", "--local-rank", dest="local_rank", type=int, default=0)
+    p.add_argument("--ngpu", type=int, default=None, help="world size (defaults to WORLD_SIZE from the launcher)")
+    g = p.add_argument_group("supervised-training additions")
+    g.add_argument("--optimizer", type=str, default="sgd", choices=["sgd", "lars"])
+    g.add_argument("--grad_compress", type=str, default="none", choices=["none", "bf16"],
+                   help="gradient bucket all-reduce payload: fp32 or bf16")
+    g.add_argument("--resume", type=str, default="", help="resume model+optimizer+epoch from a ckpt of this trainer")
+    g.add_argument("--label_frac", type=float, default=1.0,
+                   help="train on a class-balanced subset: per class ceil(f * n_c) images, drawn once from "
+                        "--seed (the semi-supervised protocol: 0.01, 0.1)")
+    g.add_argument("--val_freq", type=int, default=1, help="validate every N epochs and after the last epoch")
+    g.add_argument("--val_batch_size", type=int, default=256)
+    g.add_argument("--n_cls", type=int, default=0, help="number of classes (0 = from the dataset)")
+    g.add_argument("--micro_batch", type=int, default=0, help="not supported by this trainer")
+    g.add_argument("--blur_p", type=float, default=0.0,
+                   help="> 0: the SimCLR augmentation with one view (colour jitter, grayscale and this "
+                        "Gaussian-blur probability: the ImageNet recipe) instead of crop + flip")
+    g.add_argument("--blur_kernel", type=int, default=0, help="blur kernel size, odd (0 = automatic)")
+    g.add_argument("--blur_sigma", type=float, nargs=2, default=[0.1, 2.0], metavar=("LO", "HI"))
+    _add_eval_flags(g)
+    _add_common_new_flags(p)
+    return p
+
+
+def parse_ce(argv: Optional[Sequence[str]] = None, make_dirs: bool = True,
+             now: Optional[datetime.datetime] = None):
+    opt = ce_parser().parse_args(argv)
+    if opt.cuda_graph or opt.micro_batch:
+        raise ValueError("main_ce.py supports neither --cuda_graph nor --micro_batch")
+    if not 0.0 < opt.label_frac <= 1.0:
+        raise ValueError(f"--label_frac {opt.label_frac} must be in (0, 1]")
+    if opt.val_freq < 1 or opt.size < 1 or opt.n_cls < 0:
+        raise ValueError("--val_freq >= 1, --size >= 1 and --n_cls >= 0 are required")
+    opt.blur_sigma = tuple(opt.blur_sigma)
+    if not 0.0 <= opt.blur_p <= 1.0 or opt.blur_kernel < 0 or not 0.0 < opt.blur_sigma[0] <= opt.blur_sigma[1]:
+        raise ValueError("--blur_p in [0, 1], --blur_kernel >= 0 and --blur_sigma 0 < LO <= HI are required")
+    if opt.dataset == "path":
+        if opt.mean is None or opt.std is None:
+            raise ValueError("--dataset path needs --mean and --std")
+        if not opt.synthetic and (opt.data_folder is None or opt.val_folder is None):
+            raise ValueError("--dataset path needs --data_folder and --val_folder (or --synthetic)")
+        _check_val_folder(opt)
+    rank, local_rank, world = env_rank_info(opt.local_rank)
+    opt.rank, opt.local_rank = rank, local_rank
+    if opt.ngpu is None:
+        opt.ngpu = world
+    opt.world_size = opt.ngpu
+    if opt.data_folder is None:
+        opt.data_folder = "./datasets/"
+    _finish_common(opt, True)
+    opt.model_name = "SupCE_{}_{}_lr_{}_decay_{}_bsz_{}_trial_{}".format(
+        opt.dataset, opt.model, opt.learning_rate, opt.weight_decay, opt.batch_size, opt.trial)
+    if opt.label_frac < 1.0:
+        opt.model_name = f"{opt.model_name}_frac_{opt.label_frac}"
+    if opt.cosine:
+        opt.model_name = f"{opt.model_name}_cosine"
+    if opt.batch_size > 256:
+        opt.warm = True
+    _warm_fields(opt)
+    now = now or datetime.datetime.now()
+    conf_work_path = f"{opt.dataset}_" + now.strftime("%m%d_%H%M") + "_"
+    opt.conf_work_path = conf_work_path
+    opt.model_path = os.path.join(opt.work_dir, f"{opt.dataset}_models")
+    opt.tb_path = os.path.join(opt.work_dir, f"{opt.dataset}_tensorboard")
+    opt.tb_folder = os.path.join(opt.tb_path, conf_work_path + opt.model_name)
+    opt.save_folder = os.path.join(opt.model_path, conf_work_path + opt.model_name)
+    if make_dirs and opt.rank == 0:
+        if os.path.isdir(opt.save_folder) and not opt.resume:
+            opt.save_folder = unique_dir(opt.save_folder)
+            opt.tb_folder = unique_dir(opt.tb_folder)
+        os.makedirs(opt.tb_folder, exist_ok=True)
+        os.makedirs(opt.save_folder, exist_ok=True)
+    if opt.dataset == "path":
+        opt.mean_t, opt.std_t = parse_tuple(opt.mean), parse_tuple(opt.std)
+    else:
+        opt.mean_t, opt.std_t = DATASET_STATS[opt.dataset]
+    # path: the class count comes from the dataset at engine start
+    if not opt.n_cls:
+        opt.n_cls = N_CLASSES.get(opt.dataset, 0)
+    if opt.batch_size % opt.world_size != 0:
+        raise ValueError(f"--batch_size {opt.batch_size} must be divisible by world size {opt.world_size}")
+    opt.local_batch = opt.batch_size // opt.world_size
     return opt

@@ -49,3 +49,23 @@ class DistributedIndexSampler:
             idx = idx.to(device, non_blocking=True)
         for i in range(len(self)):
             yield idx[i * self.b:(i + 1) * self.b]
+
+
+def label_subset(labels: np.ndarray, frac: float, seed: int = 0) -> np.ndarray:
+    """Class-balanced subset for ``--label_frac``: per class ``ceil(frac · n_c)`` indices taken from
+    the front of a seeded permutation of that class's images, returned in ascending order. A
+    function of (labels, frac, seed) only, so every rank draws the same subset; ``frac`` 1 is the
+    whole set."""
+    if not 0.0 < frac <= 1.0:
+        raise ValueError(f"label fraction {frac} must be in (0, 1]")
+    labels = np.asarray(labels)
+    if frac >= 1.0:
+        return np.arange(labels.shape[0], dtype=np.int64)
+    g = np.random.default_rng(seed)
+    keep = []
+    for c in np.unique(labels):
+        idx = np.flatnonzero(labels == c)
+        # (the 1e-9 keeps ceil(0.1 · 30) at 3 where the product rounds to 3.0000000000000004)
+        k = min(idx.size, int(np.ceil(frac * idx.size - 1e-9)))
+        keep.append(g.permutation(idx)[:k])
+    return np.sort(np.concatenate(keep)).astype(np.int64)

@@ -1,0 +1,93 @@
+"""Trainable classifier + cross-entropy (reference main_ce.py / networks/resnet_big.py:184-193:
+``SupCEResNet.fc`` on the encoder features, ``nn.CrossEntropyLoss`` (mean), ``util.accuracy``
+top-1 / top-5) as ONE autograd node of two launches per step (csrc/kernels/linear_ce.hip).
+
+* forward: ``linear_ce_fwd`` — logits, per-row loss and top-1/5 hits, and
+  dz = (softmax − onehot) / B, the gradient of the mean loss with respect to the logits;
+* backward: ``ce_head_bwd`` — dX = gout·dz·W returned to autograd, dW += gout·dzᵀ·x and
+  db += gout·Σ_b dz accumulated straight into the parameter sinks (``ops/sinks.py``: the views
+  of the flat gradient buffer), and the row statistics summed in row order.
+
+fp32 throughout and deterministic (no atomics, fixed summation order).
+
+The statistics are summed by the backward launch: ``loss`` and ``stats`` hold their values once
+``loss.backward()`` has been queued (stream order), which is where a training step reads them.
+A forward that records no graph (``torch.no_grad()``, or nothing requires a gradient) sums them
+itself, so its outputs are valid at once.
+
+Unsupported shapes (K ≠ 64·2^j, K > 2048, C > 1024), CPU tensors and the ``torch`` backend use
+``F.linear`` + ``F.cross_entropy``: the same values through stock torch ops.
+"""
+from __future__ import annotations
+
+from typing import Tuple
+
+import torch
+import torch.nn.functional as F
+
+from . import _ext, sinks
+
+
+def supported(fc: torch.nn.Linear) -> bool:
+    """Whether the native node can run this classifier (its launchers refuse anything else)."""
+    if not fc.weight.is_cuda or fc.bias is None or fc.weight.dtype != torch.float32 or not _ext.available():
+        return False
+    k, c = fc.in_features, fc.out_features
+    return k % 64 == 0 and k <= 2048 and ((k // 64) & (k // 64 - 1)) == 0 and 1 <= c <= 1024
+
+
+class _ClassifierCE(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, feat, labels, fc, record, *params):
+        m = _ext.require()
+        x = feat.detach().float().contiguous()
+        w = fc.weight.detach()
+        # record: a backward will follow (decided by the caller: grad mode is off in here)
+        need = [ctx.needs_input_grad[0], any(ctx.needs_input_grad[4:])]
+        logits, dz, rowstat, stats, loss = m.ce_head_fwd(x, w, fc.bias.detach(), labels, not record)
+        ctx.save_for_backward(x, dz, w, rowstat, stats, loss)
+        ctx.fc = fc
+        ctx.params = params
+        ctx.need = need
+        ctx.feat_dtype = feat.dtype
+        ctx.mark_non_differentiable(stats, logits)
+        return loss, stats, logits
+
+    @staticmethod
+    def backward(ctx, gout, _gstats, _glogits):
+        x, dz, w, rowstat, stats, loss = ctx.saved_tensors
+        fc = ctx.fc
+        need_dx, need_dw = ctx.need
+        t = sinks.target
+        go = gout.detach().float().contiguous()
+        dx = _ext.require().ce_head_bwd(x, dz, w, go, rowstat, stats, loss,
+                                        t(fc.weight) if need_dw else None, t(fc.bias) if need_dw else None, need_dx)
+        if need_dw:
+            sinks.notify(ctx.params)
+        return (dx.to(ctx.feat_dtype) if dx is not None else None, None, None, None) + (None,) * len(ctx.params)
+
+
+def classifier_ce_logits(feat: torch.Tensor, fc: torch.nn.Linear, labels: torch.Tensor,
+                         native: bool = True) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(loss, stats, logits) of ``F.cross_entropy(fc(feat), labels)``: ``loss`` the batch mean,
+    ``stats`` = [Σ_rows CE, top-1 hits, top-5 hits] (fp32, no gradient), ``logits`` [B, C] (no
+    gradient). ``native=False`` forces the torch ops."""
+    labels = labels.long()
+    if native and feat.is_cuda and supported(fc):
+        record = torch.is_grad_enabled() and (feat.requires_grad or fc.weight.requires_grad or fc.bias.requires_grad)
+        return _ClassifierCE.apply(feat, labels.contiguous(), fc, record, fc.weight, fc.bias)
+    logits = F.linear(feat.float(), fc.weight, fc.bias)
+    loss = F.cross_entropy(logits, labels)
+    with torch.no_grad():
+        z = logits.detach()
+        # the kernel's rank rule: a row hits@k when fewer than k logits exceed the label's
+        above = (z > z.gather(1, labels[:, None])).sum(1)
+        stats = torch.stack([loss.detach() * labels.numel(), (above < 1).sum().float(), (above < 5).sum().float()])
+    return loss, stats.to(loss.dtype), logits.detach()
+
+
+def classifier_ce(feat: torch.Tensor, fc: torch.nn.Linear, labels: torch.Tensor,
+                  native: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``(loss, stats)`` — see :func:`classifier_ce_logits`."""
+    loss, stats, _ = classifier_ce_logits(feat, fc, labels, native)
+    return loss, stats
