@@ -11,7 +11,7 @@ Several ranks: every rank encodes a contiguous 1/W slice of the bank and of the 
 last slices padded to equal length by repeating the final image; pad rows are dropped by
 index after the gather), the bank features are all-gathered, the hit counts summed.
 
-ImageFolder runs (``resize > 0``): either store may be ragged (flat bytes + ``offs``/``hw``), and
+ImageFolder runs (``aug.resize > 0``): either store may be ragged (data/store.py), and
 every image goes through Resize(resize) + CenterCrop(size) on the GPU (AugConfig.center_crop), so
 the bank is the training store as it is resident for pretraining; no cropped copy is made.
 """
@@ -22,29 +22,24 @@ from typing import Optional, Tuple
 import torch
 import torch.nn.functional as F
 
-from ..data.augment import AugConfig, augment, nhwc8_to_nchw
+from ..data.augment import AugConfig
+from ..data.store import DeviceStore
 from ..ops import knn as knn_ops
+from ..ops.linear_probe import eval_encoder
 from ..parallel import comm
 
 
 class KnnEvaluator:
-    def __init__(self, model: torch.nn.Module, backend: str, precision: str, bank_x: torch.Tensor,
-                 bank_y: torch.Tensor, val_x: torch.Tensor, val_y: torch.Tensor, mean, std, size: int, n_cls: int,
-                 k: int = 200, T: float = 0.1, batch_size: int = 512, runner=None, *, bank_offs=None, bank_hw=None,
-                 val_offs=None, val_hw=None, resize: int = 0):
+    def __init__(self, model: torch.nn.Module, backend: str, precision: str, bank: DeviceStore, val: DeviceStore,
+                 aug: AugConfig, n_cls: int, k: int = 200, T: float = 0.1, batch_size: int = 512, runner=None):
         self.model = model
         self.backend = backend
         self.precision = precision
-        self.bank_x, self.bank_y = bank_x, bank_y.long()
-        self.val_x, self.val_y = val_x, val_y.long()
-        if (bank_offs is None) != (bank_hw is None) or (val_offs is None) != (val_hw is None):
-            raise ValueError("offs and hw of a ragged store must be given together")
-        if resize <= 0 and (bank_offs is not None or val_offs is not None):
+        self.bank, self.val = bank, val
+        self._bank_y, self._val_y = bank.labels.long(), val.labels.long()
+        if aug.resize <= 0 and (bank.ragged or val.ragged):
             raise ValueError("a ragged store needs resize > 0 (Resize + CenterCrop)")
-        # store tensor -> its (offs, hw), (None, None) for a dense one
-        self._ragged = {id(self.bank_x): (bank_offs, bank_hw), id(self.val_x): (val_offs, val_hw)}
-        self.aug = (AugConfig.center_crop(size, mean, std, resize) if resize > 0
-                    else AugConfig.evaluation(size, mean, std))
+        self.aug = aug          # AugConfig.evaluation, or .center_crop of an ImageFolder run
         self.n_cls = int(n_cls)
         self.k = int(k)
         self.T = float(T)
@@ -56,47 +51,23 @@ class KnnEvaluator:
         self.last_bank: Optional[torch.Tensor] = None   # gathered bank features of the last evaluate()
 
     # --------------------------------------------------------------------------------
-    @torch.no_grad()
-    def _count(self, images: torch.Tensor) -> int:
-        """Images in a store: by index, not by the (flat, when ragged) tensor's first dimension."""
-        offs = self._ragged.get(id(images), (None, None))[0]
-        return int(offs.shape[0]) if offs is not None else int(images.shape[0])
-
-    def _encode_range(self, images: torch.Tensor, lo: int, hi: int, encode) -> torch.Tensor:
+    def _encode_range(self, store: DeviceStore, lo: int, hi: int, encode) -> torch.Tensor:
         """Features of images lo..hi-1 (indices >= the image count repeat the last image)."""
-        n = self._count(images)
-        offs, hw = self._ragged.get(id(images), (None, None))
-        dev = images.device
+        n = len(store)
+        dev = store.images.device
         outs = []
         for s in range(lo, hi, self.batch_size):
             idx = torch.arange(s, min(s + self.batch_size, hi), device=dev).clamp_(max=n - 1)
-            x = augment(images, idx, self.aug, 0, offs, hw)
-            outs.append(F.normalize(encode(x).float(), dim=1))
+            outs.append(F.normalize(encode(store.views(idx, self.aug, 0)), dim=1))
         return torch.cat(outs) if outs else torch.zeros((0, 0), device=dev)
 
-    def _encoder_fn(self):
-        """The eval-mode encoder forward and a function that undoes what it had to set."""
-        if self.backend == "native":
-            from ..ops.linear_probe import FoldedEncoder
-            # rebuilt at every evaluation: the encoder trains between evaluations
-            folded = FoldedEncoder(self.model.encoder)
-            return folded, (lambda: None)
-        enc = self.model.encoder
-        flags = [(m, m.training) for m in enc.modules()]
-        enc.eval()
-
-        def restore():
-            for m, t in flags:
-                m.training = t
-
-        return (lambda x: self.runner.encode(nhwc8_to_nchw(x), training=False)), restore
-
     @torch.no_grad()
-    def extract(self, images: torch.Tensor, lo: int = 0, hi: Optional[int] = None) -> torch.Tensor:
-        """L2-normalised fp32 encoder features (not the projection head's) of ``images[lo:hi]``."""
-        encode, restore = self._encoder_fn()
+    def extract(self, store: DeviceStore, lo: int = 0, hi: Optional[int] = None) -> torch.Tensor:
+        """L2-normalised fp32 encoder features (not the projection head's) of images lo..hi-1 of ``store``."""
+        # the fold of NOW: the encoder trains between evaluations
+        encode, restore = eval_encoder(self.model, self.backend, self.runner)
         try:
-            return self._encode_range(images, lo, self._count(images) if hi is None else hi, encode)
+            return self._encode_range(store, lo, len(store) if hi is None else hi, encode)
         finally:
             restore()
 
@@ -104,13 +75,14 @@ class KnnEvaluator:
     def evaluate(self) -> Tuple[float, float]:
         """(top-1, top-5) of the validation set in percent; identical on every rank."""
         W, r = comm.world_size(), comm.rank()
-        nb, nv = self._count(self.bank_x), self._count(self.val_x)
+        nb, nv = len(self.bank), len(self.val)
         per_b, per_v = (nb + W - 1) // W, (nv + W - 1) // W
-        encode, restore = self._encoder_fn()
+        # the fold of NOW: the encoder trains between evaluations
+        encode, restore = eval_encoder(self.model, self.backend, self.runner)
         try:
-            bank_f = self._encode_range(self.bank_x, r * per_b, (r + 1) * per_b, encode)
+            bank_f = self._encode_range(self.bank, r * per_b, (r + 1) * per_b, encode)
             v_lo, v_hi = min(r * per_v, nv), min((r + 1) * per_v, nv)
-            q = self._encode_range(self.val_x, v_lo, v_hi, encode)
+            q = self._encode_range(self.val, v_lo, v_hi, encode)
         finally:
             restore()
         if W > 1:
@@ -119,8 +91,8 @@ class KnnEvaluator:
         hits = torch.zeros(2, dtype=torch.float32, device=bank_f.device)
         if v_hi > v_lo:
             native = self.backend == "native"
-            _, st = knn_ops.knn_classify(q, bank_f, self.bank_y, self.n_cls, self.k, self.T,
-                                         labels=self.val_y[v_lo:v_hi],
+            _, st = knn_ops.knn_classify(q, bank_f, self._bank_y, self.n_cls, self.k, self.T,
+                                         labels=self._val_y[v_lo:v_hi],
                                          backend="auto" if native else "torch")
             hits = st.to(torch.float32)
         if W > 1:

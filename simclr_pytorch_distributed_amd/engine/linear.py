@@ -21,20 +21,20 @@ import time
 from typing import Optional
 
 import torch
-import torch.nn.functional as F
 
-from ..data.augment import AugConfig, augment, default_resize, nhwc8_to_nchw
-from ..data.datasets import build_dataset
+from ..data.augment import AugConfig
 from ..data.sampler import DistributedIndexSampler
+from ..data.store import probe_stores
 from ..models.executor import ModelRunner
 from ..models.resnet import LinearClassifier, SupConResNet
+from ..ops import linear_probe
 from ..optim.schedules import adjust_learning_rate, warmup_learning_rate
 from ..parallel import comm
 from ..utils.logging import setup_logging
 from ..utils.meters import AverageMeter, accuracy
 from ..utils.profiling import PhaseTimer
 from . import checkpoint as ckpt_mod
-from .pretrain import resolve_backend, step_seed
+from .base import resolve_backend, step_seed
 
 
 class LinearEngine:
@@ -62,55 +62,23 @@ class LinearEngine:
             p.requires_grad_(False)
         self.model = model
         self.runner = ModelRunner(model, self.backend, opt.precision)
-        nw = getattr(opt, "num_workers", 1)
-        size = getattr(opt, "size", 32)
-        # a real ImageFolder: native-resolution ragged training store (RandomResizedCrop on the
-        # original pixels), validation store capped at the Resize target, Resize + CenterCrop on
-        # the GPU; CIFAR and --synthetic: dense stores, normalize only
-        folder = opt.dataset == "path" and not opt.synthetic
-        self.resize = (getattr(opt, "resize", 0) or default_resize(size)) if folder else 0
-        tr = build_dataset(opt.dataset, opt.data_folder, True, opt.synthetic, opt.synthetic_size, size, opt.seed,
-                           native=folder, workers=nw)
-        va = build_dataset(opt.dataset, opt.val_folder if folder else opt.data_folder, False, opt.synthetic,
-                           opt.synthetic_size, size, opt.seed, workers=nw, eval_resize=self.resize)
-        if folder and tr.classes != va.classes:
-            raise ValueError("--val_folder has other classes than --data_folder")
-        if not opt.n_cls:
-            opt.n_cls = max(tr.num_classes, va.num_classes)
-        self.tr_x, self.tr_y = torch.from_numpy(tr.images).to(dev), torch.from_numpy(tr.labels).to(dev)
-        self.va_x, self.va_y = torch.from_numpy(va.images).to(dev), torch.from_numpy(va.labels).to(dev)
-        self.tr_offs = torch.from_numpy(tr.offsets).to(dev) if tr.ragged else None
-        self.tr_hw = torch.from_numpy(tr.sizes).to(dev) if tr.ragged else None
-        self.va_offs = torch.from_numpy(va.offsets).to(dev) if va.ragged else None
-        self.va_hw = torch.from_numpy(va.sizes).to(dev) if va.ragged else None
-        self.n_val = len(va)
+        self.train, self.val, self.resize, self.aug_val, opt.n_cls = probe_stores(opt, dev)
         # the reference DataLoader keeps the last partial batch (main_ce.py set_loader)
-        self.sampler = DistributedIndexSampler(len(tr), opt.batch_size, 1, 0, seed=opt.seed, drop_last=False)
-        self.aug_train = AugConfig.linear_train(size, opt.mean_t, opt.std_t)
-        self.aug_val = (AugConfig.center_crop(size, opt.mean_t, opt.std_t, self.resize) if folder
-                        else AugConfig.evaluation(size, opt.mean_t, opt.std_t))
+        self.sampler = DistributedIndexSampler(len(self.train), opt.batch_size, 1, 0, seed=opt.seed, drop_last=False)
+        self.aug_train = AugConfig.linear_train(getattr(opt, "size", 32), opt.mean_t, opt.std_t)
         self.classifier = LinearClassifier(opt.model, opt.n_cls).to(dev)
-        self.folded = None
+        # the encoder is frozen: the native fold is computed once
+        self.encode, _ = linear_probe.eval_encoder(model, self.backend, self.runner)
+        self.folded = self.encode if self.backend == "native" else None      # the FoldedEncoder, when there is one
         self.native_ce = None
-        if self.backend == "native":
-            from ..ops import linear_probe
-            self.folded = linear_probe.FoldedEncoder(model.encoder)
-            if linear_probe.supported(self.classifier):
-                self.native_ce = linear_probe.NativeLinearCE(self.classifier, opt.momentum, opt.weight_decay)
+        if self.backend == "native" and linear_probe.supported(self.classifier):
+            self.native_ce = linear_probe.NativeLinearCE(self.classifier, opt.momentum, opt.weight_decay)
         self.criterion = torch.nn.CrossEntropyLoss()
         self.optimizer = torch.optim.SGD(self.classifier.parameters(), lr=opt.learning_rate, momentum=opt.momentum,
                                          weight_decay=opt.weight_decay)
         from ..utils.tb import Logger
         self.logger = Logger(opt.tb_folder, flush_secs=2)
         self.prof = PhaseTimer(getattr(opt, "profile", False), dev)
-
-    def _features(self, x):
-        if self.backend == "torch":
-            x = nhwc8_to_nchw(x)
-        with torch.no_grad():
-            if self.folded is not None:
-                return self.folded(x)
-            return self.runner.encode(x, training=False).float()
 
     def _classify(self, feats, labels, train: bool):
         """(logits, loss, acc1, acc5) of a batch — device tensors; train: + the SGD step."""
@@ -148,13 +116,12 @@ class LinearEngine:
             dtm.update(time.time() - end)
             ph = self.prof.phase
             with ph("augment"):
-                x = augment(self.tr_x, idx, self.aug_train, step_seed(opt.seed, epoch, idx_i, 0), self.tr_offs,
-                            self.tr_hw)
-                labels = self.tr_y[idx]
+                x = self.train.views(idx, self.aug_train, step_seed(opt.seed, epoch, idx_i, 0))
+                labels = self.train.labels[idx]
             bsz = labels.shape[0]
             warmup_learning_rate(opt, epoch, idx_i, iters, self.optimizer)
             with ph("encoder"):
-                feats = self._features(x)
+                feats = self.encode(x)
             with ph("classifier"):
                 output, loss, acc1, acc5 = self._classify(feats, labels, True)
                 win += torch.stack([loss.double() * bsz, acc1.double() * bsz, acc5.double() * bsz,
@@ -182,14 +149,14 @@ class LinearEngine:
     def validate(self):
         opt = self.opt
         self.classifier.eval()
-        n = self.n_val
+        n = len(self.val)
         losses, top1, top5 = AverageMeter(), AverageMeter(), AverageMeter()
         vb = opt.val_batch_size
         for i, s in enumerate(range(0, n, vb)):
             idx = torch.arange(s, min(s + vb, n), device=self.device)
-            x = augment(self.va_x, idx, self.aug_val, 0, self.va_offs, self.va_hw)
-            labels = self.va_y[idx]
-            output, loss, acc1, acc5 = self._classify(self._features(x), labels, False)
+            x = self.val.views(idx, self.aug_val, 0)
+            labels = self.val.labels[idx]
+            output, loss, acc1, acc5 = self._classify(self.encode(x), labels, False)
             bsz = labels.shape[0]
             losses.update(loss.item(), bsz)
             top1.update(acc1.item(), bsz)
@@ -206,10 +173,8 @@ class LinearEngine:
         from .knn import KnnEvaluator
         opt = self.opt
         t0 = time.time()
-        ev = KnnEvaluator(self.model, self.backend, opt.precision, self.tr_x, self.tr_y, self.va_x, self.va_y,
-                          opt.mean_t, opt.std_t, getattr(opt, "size", 32), opt.n_cls, opt.knn_k, opt.knn_t,
-                          runner=self.runner if self.backend != "native" else None, bank_offs=self.tr_offs,
-                          bank_hw=self.tr_hw, val_offs=self.va_offs, val_hw=self.va_hw, resize=self.resize)
+        ev = KnnEvaluator(self.model, self.backend, opt.precision, self.train, self.val, self.aug_val, opt.n_cls,
+                          opt.knn_k, opt.knn_t, runner=self.runner if self.backend != "native" else None)
         acc1, acc5 = ev.evaluate()
         logging.info("kNN: epoch {} Acc@1 {:.2f} Acc@5 {:.2f} ({:.2f}s)".format(0, acc1, acc5, time.time() - t0))
         self.logger.log_value("knn/val_acc1", acc1, 0)

@@ -19,112 +19,45 @@ from __future__ import annotations
 
 import contextlib
 import logging
-import math
 import os
 import sys
 import time
-from typing import Optional
 
 import torch
-import torch.distributed as dist
 
-from ..data.augment import AugConfig, augment, nhwc8_to_nchw
-from ..data.augment import gpu_augment as augment_gpu
+from ..data.augment import AugConfig
 from ..data.datasets import build_dataset
 from ..data.sampler import DistributedIndexSampler
+from ..data.store import DeviceStore, probe_stores
 from ..losses.supcon import DistributedContrastiveLoss
-from ..models.executor import ModelRunner
 from ..models.resnet import SupConResNet
 from ..ops import _ext
-from ..optim.flat import FlatParams, FusedSGD, build_optimizer
-from ..optim.schedules import adjust_learning_rate, warmup_learning_rate
+from ..optim.flat import FusedSGD
 from ..parallel import comm
-
-_ZERO_SIDE = os.environ.get("SDX_ZERO_SIDE", "1") != "0"
-_NORM_SIDE = os.environ.get("SDX_NORM_SIDE", "1") != "0"
-from ..parallel.ddp import GradBucketReducer
-from ..utils.logging import setup_logging
-from ..utils.meters import AverageMeter
 from ..utils.faults import maybe_inject
+from ..utils.meters import AverageMeter
 from ..utils.profiling import PhaseTimer
 from . import checkpoint as ckpt_mod
+from .base import TrainEngine, resolve_backend, step_seed  # noqa: F401  (importable from here as before)
+
+_NORM_SIDE = os.environ.get("SDX_NORM_SIDE", "1") != "0"
 
 
-def resolve_backend(requested: str, device: torch.device, stem: str = "cifar") -> str:
-    if requested == "torch":
-        return "torch"
-    native_ok = device.type == "cuda" and _ext.available()
-    if requested == "native":
-        if not native_ok:
-            _ext.require()
-            raise RuntimeError("native backend needs a GPU")
-        return "native"
-    return "native" if native_ok else "torch"
-
-
-def _null():
-    import contextlib
-    return contextlib.nullcontext()
-
-
-def step_seed(base: int, epoch: int, idx: int, rank: int) -> int:
-    return (base * 1000003 + epoch * 100003 + idx * 17 + rank * 7919) & ((1 << 62) - 1)
-
-
-_PRIO_STREAMS = {}
-
-
-def _priority_stream(dev: torch.device) -> torch.cuda.Stream:
-    key = dev.index if dev.index is not None else torch.cuda.current_device()
-    st = _PRIO_STREAMS.get(key)
-    if st is None:
-        st = _PRIO_STREAMS[key] = torch.cuda.Stream(device=dev, priority=-1)
-    return st
-
-
-class PretrainEngine:
-    def __init__(self, opt, device: Optional[torch.device] = None):
-        self.opt = opt
-        rank, local_rank, world, dev = comm.init_distributed(opt.dist_backend, getattr(opt, "comm_timeout", 600.0), device=device)
-        self.rank, self.world, self.device = rank, world, dev
-        self.stream = None
-        if dev.type == "cuda" and os.environ.get("SDX_STREAM_PRIO", "1") != "0":
-            # the whole step on a high-priority stream: the critical path (forward, BN,
-            # dgrad chain) is dispatched ahead of the default-priority wgrad side stream.
-            # 12.52 -> 12.43 ms/step same box, 4 alternating rounds (profiles/knob_sweep_r3.txt).
-            # One stream per device and process, shared by every engine built in it.
-            self.stream = _priority_stream(dev)
-            torch.cuda.set_stream(self.stream)
-        if opt.ngpu != world and world > 1:
-            logging.warning(f"--ngpu {opt.ngpu} != launcher WORLD_SIZE {world}; using {world}")
-        opt.world_size = world
-        opt.local_batch = opt.batch_size // world
-        setup_logging(opt.save_folder, rank)
-        if rank == 0:
-            logging.info(f"create {opt.conf_work_path} ...")
-        torch.manual_seed(opt.seed)
-        self.backend = resolve_backend(opt.backend, dev, opt.stem)
-
+class PretrainEngine(TrainEngine):
+    def _build_model(self):
+        opt = self.opt
         model = SupConResNet(opt.model, opt.head, opt.feat_dim, opt.stem)
         if opt.ckpt:
             sd = ckpt_mod.load_checkpoint(opt.ckpt)["model"]
             ckpt_mod.load_model_state(model, sd)
             logging.info(f"load model from {opt.ckpt} ...")
-        self.sync_group = None
-        if opt.syncBN and world > 1:
-            if self.backend == "torch":
-                from ..parallel.syncbn import convert_sync_bn
-                model = convert_sync_bn(model)
-                self.syncbn_transport = "torch-syncbn"
-            else:
-                self.sync_group = dist.group.WORLD
-                self._setup_syncbn_comm(opt, dev)
-                if self.syncbn_transport == "none":
-                    self.syncbn_transport = "process-group"
-        if world > 1 and self.backend == "native":
+        return model
+
+    def _setup_more_comm(self, opt, dev):
+        if self.world > 1 and self.backend == "native":
             self._setup_gather_comm(opt, dev)
         emu = int(os.environ.get("SDX_SYNCBN_EMU", "0") or 0)
-        if emu > 1 and world == 1 and self.backend == "native" and dev.type == "cuda":
+        if emu > 1 and self.world == 1 and self.backend == "native" and dev.type == "cuda":
             # SyncBN over `emu` identical virtual ranks on this GPU (comm.EmulatedGroup):
             # SDX_SYNCBN_EMU_KIND=fused (default, the xGMI fused exchange) | emu (reduce ->
             # x·W -> finalize, the kernel sequence of the RCCL path minus the collective)
@@ -135,88 +68,59 @@ class PretrainEngine:
             comm.set_native_small_comm(self.sync_group, h)
             self.syncbn_transport = f"emulated-{emu}-{kind}"
             logging.info(f"SyncBN emulated over {emu} virtual ranks ({kind})")
-        model = model.to(dev)
-        if dev.type == "cuda":
-            model = model.to(memory_format=torch.channels_last)
-        self.model = model
-        self.flat = FlatParams(model)
-        self.optimizer = build_optimizer(opt.optimizer, self.flat, opt.learning_rate, opt.momentum,
-                                         opt.weight_decay, backend="torch" if self.backend == "torch" else "auto")
+
+    def _early_step(self):
         # SDX_EARLY_STEP=1 (native SGD): each bucket's update runs as soon as its gradients are
         # final (after its collective with several ranks), overlapping the rest of backward.
         # Off by default: on one MI355X the step's tail shrinks by ~85 us but the update
         # kernels slow the concurrent critical-path backward kernels more (12.31 -> 12.44-12.60
         # ms/step same box, profiles/early_step_r3.txt)
-        early = None
-        if (isinstance(self.optimizer, FusedSGD) and self.optimizer.native and not getattr(opt, "cuda_graph", False)
+        if (isinstance(self.optimizer, FusedSGD) and self.optimizer.native and not getattr(self.opt, "cuda_graph", False)
                 and os.environ.get("SDX_EARLY_STEP", "0") == "1"):
-            early = self.optimizer.apply_range
-        self.reducer = (GradBucketReducer(self.flat, early_step=early, compress=getattr(opt, "grad_compress", "none"))
-                        if (world > 1 or early is not None) else None)
-        self.optimizer.grad_scale = (1.0 / world) if opt.grad_semantics == "ref" else 1.0
-        self.runner = ModelRunner(model, self.backend, opt.precision, self.sync_group, master=self.flat.flat)
-        self.criterion = DistributedContrastiveLoss(opt.method, opt.temp, opt.base_temperature, opt.contrast_mode,
-                                                    backend="native" if self.backend == "native" else "torch")
-        # data: whole uint8 dataset resident on the device
+            return self.optimizer.apply_range
+        return None
+
+    def _grad_scale(self):
+        return super()._grad_scale() if self.opt.grad_semantics == "ref" else 1.0
+
+    def _build_data(self):
+        # data: whole uint8 dataset resident on the device; an ImageFolder as a native-resolution
+        # ragged store (RandomResizedCrop on original pixels)
+        opt = self.opt
         ds = build_dataset(opt.dataset, opt.data_folder, True, opt.synthetic, opt.synthetic_size, opt.size, opt.seed,
                            native=True, workers=opt.num_workers)
-        self.data = torch.from_numpy(ds.images).to(dev)
-        # ImageFolder: native-resolution ragged store (RandomResizedCrop on original pixels)
-        self.data_offs = torch.from_numpy(ds.offsets).to(dev) if ds.ragged else None
-        self.data_hw = torch.from_numpy(ds.sizes).to(dev) if ds.ragged else None
-        self.labels = torch.from_numpy(ds.labels).to(dev)
-        self.sampler = DistributedIndexSampler(len(ds), opt.local_batch, world, rank, seed=opt.seed)
+        self.train = DeviceStore.from_dataset(ds, self.device)
+        self.sampler = DistributedIndexSampler(len(ds), opt.local_batch, self.world, self.rank, seed=opt.seed)
         self.aug = AugConfig.simclr(opt.size, opt.mean_t, opt.std_t, blur_p=getattr(opt, "blur_p", 0.0),
                                     blur_kernel=getattr(opt, "blur_kernel", 0),
                                     blur_sigma=getattr(opt, "blur_sigma", (0.1, 2.0)))
-        self.logger = None
-        if rank == 0:
-            from ..utils.tb import Logger
-            self.logger = Logger(opt.tb_folder, flush_secs=2)
-        self.start_epoch = 1
-        self.global_step = 0
+
+    def _init_state(self):
+        opt, dev = self.opt, self.device
+        self.criterion = DistributedContrastiveLoss(opt.method, opt.temp, opt.base_temperature, opt.contrast_mode,
+                                                    backend="native" if self.backend == "native" else "torch")
         # device-resident step state (so the step body is graph-capturable)
         self.record_norm_mean = torch.zeros((), device=dev)
         self._rnm_valid = torch.zeros((), device=dev)
-        self._seed_t = torch.zeros((1,), dtype=torch.int64, device=dev)
-        self._seed_host = 0
-        self._seed_dev = False     # True once a hipGraph of the step exists (the seed then lives in _seed_t)
         self._ramp_t = torch.zeros((), device=dev)
+        self._ns_sums = None
         self._graph = None
         self._graph_stats = None
-        self.prof = PhaseTimer(getattr(opt, "profile", False), dev)
-        self.knn = None
-        if getattr(opt, "knn_freq", 0) > 0:
-            self.knn = self._build_knn(ds)
-        if getattr(opt, "resume", ""):
-            self._resume(opt.resume)
+        self._graph_failed = False
+        self.knn = self._build_knn(self.train) if getattr(opt, "knn_freq", 0) > 0 else None
 
-    def _build_knn(self, train_ds):
+    def _build_knn(self, train: DeviceStore):
         """The weighted k-NN monitor (--knn_freq): bank = the training images already resident
         on the device, queries = the validation split, loaded here once. An ImageFolder's
         native-resolution ragged store is the bank in place (Resize + CenterCrop on the GPU at
         every evaluation, no second copy); its queries are --val_folder."""
-        from ..data.augment import default_resize
         from .knn import KnnEvaluator
         opt = self.opt
-        val_folder = getattr(opt, "val_folder", None)
-        if train_ds.ragged and not val_folder:
+        if train.ragged and not getattr(opt, "val_folder", None):
             raise ValueError("--knn_freq needs a fixed-size dataset with a validation split, or --val_folder")
-        resize = (getattr(opt, "resize", 0) or default_resize(opt.size)) if train_ds.ragged else 0
-        va = build_dataset(opt.dataset, val_folder if train_ds.ragged else opt.data_folder, False, opt.synthetic,
-                           opt.synthetic_size, opt.size, opt.seed, workers=opt.num_workers, eval_resize=resize)
-        if train_ds.ragged and train_ds.classes != va.classes:
-            raise ValueError("--val_folder has other classes than --data_folder")
-        n_cls = opt.n_cls or (max(train_ds.num_classes, va.num_classes) if train_ds.ragged else
-                              int(max(int(train_ds.labels.max()), int(va.labels.max()))) + 1)
-        dev = self.device
-        return KnnEvaluator(self.model, self.backend, opt.precision, self.data, self.labels,
-                            torch.from_numpy(va.images).to(dev), torch.from_numpy(va.labels).to(dev),
-                            opt.mean_t, opt.std_t, opt.size, n_cls, opt.knn_k, opt.knn_t,
-                            runner=self.runner if self.backend != "native" else None,
-                            bank_offs=self.data_offs, bank_hw=self.data_hw,
-                            val_offs=torch.from_numpy(va.offsets).to(dev) if va.ragged else None,
-                            val_hw=torch.from_numpy(va.sizes).to(dev) if va.ragged else None, resize=resize)
+        train, val, _, aug, n_cls = probe_stores(opt, self.device, train=train, n_cls_from_labels=True)
+        return KnnEvaluator(self.model, self.backend, opt.precision, train, val, aug, n_cls, opt.knn_k, opt.knn_t,
+                            runner=self.runner if self.backend != "native" else None)
 
     def knn_eval(self, epoch: int):
         """Run the k-NN monitor, log it and (rank 0) write knn/val_acc1, knn/val_acc5."""
@@ -229,138 +133,6 @@ class PretrainEngine:
             self.logger.log_value("knn/val_acc1", acc1, epoch)
             self.logger.log_value("knn/val_acc5", acc5, epoch)
         return acc1, acc5
-
-    # ------------------------------------------------------------------------------
-    # SyncBN statistics transport actually in use (bench.py reports it): none (W=1),
-    # xgmi-fused, rccl-native, process-group (c10d collectives), emulated-W
-    syncbn_transport = "none"
-
-    def _setup_syncbn_comm(self, opt, dev):
-        """SyncBN statistics transport for the native backend (SURVEY §2.3 X4/X6, §5.8;
-        reference: main_supcon.py:222-224 converts the model to SyncBatchNorm).
-
-        Candidates, each registered as a native handle so the C++ block executor exchanges
-        each BN's sums itself on the compute stream:
-
-        * ``xgmi-fused``: the one-shot IPC arena whose FUSED path reduces, exchanges and
-          finalizes a BN's statistics in ONE launch (parallel/xgmi.py); all ranks must be
-          peers on one node.
-        * ``rccl-native``: a dedicated RCCL communicator (reduce -> ncclAllReduce ->
-          finalize per BN).
-        * ``process-group``: no native handle; the Python collective path (gloo runs).
-
-        ``--syncbn_comm auto`` (default) sets up every candidate the job can have and MEASURES
-        them on the first training batch (:meth:`autotune_syncbn`): all ranks agree on the
-        fastest one (timings MAX-reduced over ranks, so the choice is identical everywhere).
-        ``xgmi`` / ``rccl`` force one (RCCL is the fallback of both when the arena's self-check
-        fails)."""
-        want = getattr(opt, "syncbn_comm", "auto")
-        self._syncbn_cands = {}
-        if dev.type != "cuda":
-            return
-        timeout = float(getattr(opt, "comm_timeout", 600.0))
-        if want in ("xgmi", "auto"):
-            # set-up is agreed step by step across ranks (parallel/xgmi.py): either every
-            # rank gets the arena or every rank raises here and falls back together
-            try:
-                from ..parallel.xgmi import OneShotAllReduce
-                impl = OneShotAllReduce(timeout_s=timeout)
-                self._xgmi = impl
-                self._syncbn_cands["xgmi-fused"] = (impl.handle, impl)
-            except Exception as e:  # noqa: BLE001
-                (logging.warning if want == "xgmi" else logging.info)(
-                    f"one-shot xGMI exchange unavailable ({e}); using RCCL")
-        if (want == "auto" or not self._syncbn_cands) and comm.backend() == "nccl" \
-                and os.environ.get("SDX_NATIVE_SYNCBN", "1") != "0":
-            # 0 on every rank together when the dedicated communicator cannot be set up
-            handle = comm.create_rccl_small_comm(None, timeout)
-            if handle:
-                self._syncbn_cands["rccl-native"] = (handle, None)
-        if want == "auto" and comm.backend() != "nccl":
-            self._syncbn_cands["process-group"] = (0, None)
-        if not self._syncbn_cands:
-            logging.warning("SyncBN statistics use the process-group all-reduce")
-            return
-        # until the measurement: RCCL when present (the conservative transport), else the first
-        first = "rccl-native" if "rccl-native" in self._syncbn_cands else next(iter(self._syncbn_cands))
-        self._activate_syncbn(first)
-        self._syncbn_pending = want == "auto" and len(self._syncbn_cands) > 1
-        logging.info(f"SyncBN statistics: {first} (candidates {list(self._syncbn_cands)})")
-
-    _syncbn_cands: dict = {}
-    _syncbn_pending = False
-    syncbn_tune: Optional[dict] = None
-
-    def _activate_syncbn(self, name: str):
-        handle, impl = self._syncbn_cands[name]
-        comm.set_small_allreduce(None, impl)
-        comm.set_native_small_comm(None, handle)
-        self.syncbn_transport = name
-
-    def autotune_syncbn(self, idx: torch.Tensor, steps: int = 3, baseline: bool = False) -> Optional[dict]:
-        """Pick the SyncBN transport by timing real training steps on batch ``idx`` with each
-        candidate (one untimed step each first). The training state the steps touch
-        (parameters, optimizer and BN buffers, the norm EMA) is restored afterwards, so the
-        run follows the trajectory it would have had. Every rank measures its own step
-        time; the times are MAX-reduced over the ranks (the step is as slow as its slowest
-        rank) and every rank takes the argmin of the SAME reduced vector, so the choice is
-        identical everywhere. ``baseline``: also time the step with rank-local BN statistics
-        (no exchange, timing only) to report each transport's cost per exchanged BN.
-        SDX_SYNCBN_TUNE_SKEW="rank:name:ms[,...]" adds ms to a rank's measurement (tests)."""
-        self._syncbn_pending = False
-        names = list(self._syncbn_cands)
-        if self.device.type != "cuda" or (len(names) < 2 and not baseline) or not names:
-            return None
-        if baseline:
-            names = names + ["local-bn"]
-        state = [self.flat.flat, self.optimizer.buf, self.record_norm_mean, self._rnm_valid]
-        state += [t for t in self.model.buffers()]
-        if getattr(self.optimizer, "norms", None) is not None:
-            state.append(self.optimizer.norms)
-        snap = [t.detach().clone() for t in state]
-        pend = self.runner._nbt_pending
-        active = self.syncbn_transport
-        group = self.runner.sync_group
-        self._host_prelude(1, 0, 1)
-        # two interleaved passes over the candidates, the faster of each candidate's two
-        # timings kept: a drifting clock or a cold first candidate does not pick the transport
-        ms = [float("inf")] * len(names)
-        for _ in range(2):
-            for k, nm in enumerate(names):
-                if nm == "local-bn":
-                    self.runner.sync_group = None
-                else:
-                    self._activate_syncbn(nm)
-                self._step_body(idx)
-                torch.cuda.synchronize()
-                comm.barrier()
-                t0 = time.perf_counter()
-                for _ in range(steps):
-                    self._step_body(idx)
-                torch.cuda.synchronize()
-                comm.barrier()
-                ms[k] = min(ms[k], (time.perf_counter() - t0) / steps * 1e3)
-                self.runner.sync_group = group
-        with torch.no_grad():
-            for t, v in zip(state, snap):
-                t.copy_(v)
-        self.runner._nbt_pending = pend
-        for item in filter(None, os.environ.get("SDX_SYNCBN_TUNE_SKEW", "").split(",")):
-            r, nm, extra = item.split(":")
-            if int(r) == self.rank and nm in names:
-                ms[names.index(nm)] += float(extra)
-        real = [i for i, nm in enumerate(names) if nm != "local-bn"]
-        best, red = comm.agree_fastest(names, ms, eligible=real)
-        self._activate_syncbn(best if best in self._syncbn_cands else active)
-        n_bn = 2 * sum(1 for mod in self.model.encoder.modules() if isinstance(mod, torch.nn.BatchNorm2d))
-        self.syncbn_tune = {"chosen": best, "step_ms": {nm: round(v, 3) for nm, v in zip(names, red)},
-                            "exchanges_per_step": n_bn}
-        if baseline:
-            # (transport − local-BN step) per exchanged BN; within timing noise it can be ≤ 0
-            base = red[names.index("local-bn")]
-            self.syncbn_tune["us_per_bn"] = {names[i]: round((red[i] - base) * 1e3 / n_bn, 2) for i in real}
-        logging.info(f"SyncBN transport measured: {self.syncbn_tune}")
-        return self.syncbn_tune
 
     def _setup_gather_comm(self, opt, dev):
         """Native transport of the contrastive loss's embedding all-gather / reduce-scatter
@@ -377,61 +149,23 @@ class PretrainEngine:
             comm.set_native_gather_comm(None, h)
             logging.info("contrastive-loss embedding gather: dedicated RCCL communicator (native)")
 
-    def _resume(self, path):
-        st = ckpt_mod.load_checkpoint(path)
-        ckpt_mod.load_model_state(self.model, st["model"])
-        self.optimizer.load_state_dict(st["optimizer"])
-        self.start_epoch = int(st["epoch"]) + 1
-        extra = st.get("sdx_state") or {}
-        self.global_step = int(extra.get("global_step", 0))
+    def _resume_extra(self, extra):
         rnm = extra.get("record_norm_mean")
         if rnm is not None:
             self.record_norm_mean.fill_(float(rnm))
             self._rnm_valid.fill_(1.0)
-        logging.info(f"resumed from {path} at epoch {self.start_epoch}")
 
     def _extra_state(self, epoch):
         valid = float(self._rnm_valid) > 0
-        return {"global_step": self.global_step, "epoch": epoch,
-                "record_norm_mean": float(self.record_norm_mean) if valid else None}
+        return dict(super()._extra_state(epoch), record_norm_mean=float(self.record_norm_mean) if valid else None)
+
+    def _state_tensors(self):
+        return super()._state_tensors() + [self.record_norm_mean, self._rnm_valid]
 
     # ------------------------------------------------------------------------------
-    def make_views(self, idx: torch.Tensor, epoch: int = 1, it: int = 0) -> torch.Tensor:
-        if not getattr(self.opt, "gpu_aug", 1):
-            return self._make_views_cpu(idx, epoch, it)
-        if self.backend == "native":
-            # the seed is read from device memory by the kernel (graph-replay safe)
-            # eager: the seed is a kernel argument; a captured step reads it from _seed_t at replay
-            x = augment_gpu(self.data, idx, self.aug, self._seed_host, self._seed_t if self._seed_dev else None,
-                            self.data_offs, self.data_hw)
-        else:
-            x = augment(self.data, idx, self.aug, step_seed(self.opt.seed, epoch, it, self.rank), self.data_offs,
-                        self.data_hw)
-            x = nhwc8_to_nchw(x)
-        return x
-
-    def _make_views_cpu(self, idx, epoch, it):
-        """``--gpu_aug 0``: the torch CPU pipeline (same draws as the kernel) on a host copy
-        of the dataset, ``--num_workers`` intra-op threads, then moved to the device."""
-        if getattr(self, "_cpu_data", None) is None:
-            torch.set_num_threads(max(1, int(self.opt.num_workers)))
-            self._cpu_data = self.data.cpu()
-            self._cpu_offs = self.data_offs.cpu() if self.data_offs is not None else None
-            self._cpu_hw = self.data_hw.cpu() if self.data_hw is not None else None
-        x = augment(self._cpu_data, idx.cpu(), self.aug, step_seed(self.opt.seed, epoch, it, self.rank),
-                    self._cpu_offs, self._cpu_hw)
-        if self.backend == "native":
-            return x.to(self.device, torch.bfloat16)
-        return nhwc8_to_nchw(x).to(self.device)
-
     def _host_prelude(self, epoch: int, it: int, iters: int):
-        """Per-step host-side scalars, written to device tensors the step body reads."""
+        super()._host_prelude(epoch, it, iters)
         opt = self.opt
-        warmup_learning_rate(opt, epoch, it, iters, self.optimizer)
-        self.optimizer._sync_lr()
-        self._seed_host = step_seed(opt.seed, epoch, it, self.rank)
-        if self._seed_dev:
-            self._seed_t.fill_(self._seed_host)
         if opt.sec or opt.l2reg:
             now_iter = (epoch - 1) * iters + it
             self._ramp_t.fill_(now_iter / (opt.epochs * iters))
@@ -445,13 +179,9 @@ class PretrainEngine:
             return self._step_body_gradcache(idx, epoch, it, mb)
         ph = self.prof.phase
         with ph("augment"):
-            prefetch = getattr(self.runner, "prefetch_weights", None)
-            if prefetch is not None:
-                prefetch()          # weight conversion overlaps the augmentation launch
-            zeroed = self._zero_grad_side()
-            x = self.make_views(idx, epoch, it)
+            zeroed, x = self._start_step(idx, epoch, it)
             # (SimCLR ignores labels: no gather kernel in its step)
-            labels = self.labels[idx] if opt.method == "SupCon" else None
+            labels = self.train.labels[idx] if opt.method == "SupCon" else None
         with ph("forward"):
             feats = self.runner.forward(x)
         with ph("loss"):
@@ -460,43 +190,9 @@ class PretrainEngine:
             extra = stats.pop("extra_loss")
             if extra is not None:
                 loss = loss + extra
-        with ph("backward"):
-            if zeroed is not None:
-                torch.cuda.current_stream(self.device).wait_event(zeroed)
-            else:
-                self.optimizer.zero_grad()
-            # a persistent seed gradient: no ones-fill kernel per step
-            one = getattr(self, "_one_grad", None)
-            if one is None or one.device != loss.device or one.dtype != loss.dtype:
-                one = self._one_grad = torch.ones((), device=loss.device, dtype=loss.dtype)
-            loss.backward(one)
-        if self.reducer is not None:
-            with ph("grad_sync_wait"):
-                self.reducer.finish()
-        with ph("optimizer"):
-            self.optimizer.step()
+        self._backward_and_update(loss, zeroed)
         stats["loss_local"] = loss.detach()
         return stats
-
-    def _zero_grad_side(self):
-        """Zero the gradient buffer on the wgrad side stream at the start of the step (after
-        the previous optimizer update), where it overlaps the forward instead of sitting on
-        the compute stream before the backward (SDX_ZERO_SIDE=0: there). Returns the event
-        the backward waits on, or None when it is left to the backward. The side stream's
-        weight gradients are queued behind it anyway (FIFO)."""
-        from ..ops import streams
-        if not (_ZERO_SIDE and streams.ENABLED and self.device.type == "cuda"):
-            return None
-        main = torch.cuda.current_stream(self.device)
-        s = streams.side(self.device)
-        s.wait_stream(main)
-        with torch.cuda.stream(s):
-            self.optimizer.zero_grad()
-        ev = getattr(self, "_zg_ev", None)
-        if ev is None:
-            ev = self._zg_ev = torch.cuda.Event()
-        ev.record(s)
-        return ev
 
     def _step_body_gradcache(self, idx: torch.Tensor, epoch: int, it: int, mb: int):
         """Gradient-cache step for contrastive batches larger than one encoder pass fits in
@@ -517,7 +213,7 @@ class PretrainEngine:
         ph = self.prof.phase
         with ph("augment"):
             x = self.make_views(idx, epoch, it)
-            labels = self.labels[idx]
+            labels = self.train.labels[idx]
         chunks = list(torch.split(x, mb))
         bns = [m for m in self.model.modules() if isinstance(m, torch.nn.modules.batchnorm._BatchNorm)]
         saved = [(m.running_mean.clone(), m.running_var.clone(), m.num_batches_tracked.clone())
@@ -546,31 +242,26 @@ class PretrainEngine:
             for i, c in enumerate(chunks):
                 n = c.shape[0]
                 last = i == len(chunks) - 1
-                ctx = self.reducer.no_sync() if (self.reducer is not None and not last) else _null()
+                ctx = self.reducer.no_sync() if (self.reducer is not None and not last) else contextlib.nullcontext()
                 with ctx:
                     f = self.runner.forward(c)
                     f.backward(gfeat[off:off + n].to(f.dtype))
                 off += n
-        if self.reducer is not None:
-            with ph("grad_sync_wait"):
-                self.reducer.finish()
-        with ph("optimizer"):
-            self.optimizer.step()
+        self._reduce_and_update()
         stats["loss_local"] = loss.detach()
         return stats
 
     def train_step(self, idx: torch.Tensor, epoch: int, it: int, iters: int):
         maybe_inject(self.rank, self.global_step)
-        self._host_prelude(epoch, it, iters)
-        if self._graph is not None:
-            self._idx_buf.copy_(idx, non_blocking=True)
-            self._graph.replay()
-            self.runner._nbt_pending += self._graph_nbt
-            st = self._graph_stats
-        else:
-            st = self._step_body(idx, epoch, it)
-        self.global_step += 1
-        return st
+        return super().train_step(idx, epoch, it, iters)
+
+    def _step(self, idx, epoch, it):
+        if self._graph is None:
+            return self._step_body(idx, epoch, it)
+        self._idx_buf.copy_(idx, non_blocking=True)
+        self._graph.replay()
+        self.runner._nbt_pending += self._graph_nbt
+        return self._graph_stats
 
     def enable_cuda_graph(self, idx_example: torch.Tensor, warmup: int = 2) -> bool:
         """Capture the whole training step (aug → fwd → loss → bwd → SGD) in one hipGraph.
@@ -586,51 +277,42 @@ class PretrainEngine:
             return False
         self._idx_buf = idx_example.clone()
         self._seed_dev = True
-        state = [self.flat.flat, self.optimizer.buf, self.record_norm_mean, self._rnm_valid]
-        state += [t for t in self.model.buffers()]
-        if getattr(self.optimizer, "norms", None) is not None:
-            state.append(self.optimizer.norms)
-        snap = [t.detach().clone() for t in state]
-        pend = self.runner._nbt_pending
-        self._host_prelude(1, 0, 1)
-        # The step is captured as ONE chain: the weight gradients run in line on the capture
-        # stream instead of forking to the wgrad side stream (SDX_GRAPH_SIDE=1 keeps the
-        # fork). A captured two-stream DAG replays its branches on several hardware queues
-        # with a cross-queue wait at every fork: 24.9 vs 11.9 ms eager at 256 images/GPU
-        # (23.5 ms even with per-node priorities), while each kernel replayed on its own runs
-        # at its eager speed (profiles/graph_probe_r6.txt, profiles/graph_ab_r6.txt).
-        # In line, the dedicated wgrad kernels get the whole chip (their eager block target
-        # keeps half of it for the concurrent critical path): SDX_GRAPH_WGRAD_BLOCKS, 256.
-        from ..ops import streams
-        side_prev = streams.ENABLED
-        streams.ENABLED = os.environ.get("SDX_GRAPH_SIDE", "0") == "1"
-        m = _ext.require()
-        tgt_prev = m.wgrad_block_target_set(int(os.environ.get("SDX_GRAPH_WGRAD_BLOCKS", "256"))) \
-            if not streams.ENABLED else None
-        try:
-            s = torch.cuda.Stream(device=self.device)
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):
-                for _ in range(warmup):
-                    self._step_body(self._idx_buf)
-            torch.cuda.current_stream().wait_stream(s)
-            g = torch.cuda.CUDAGraph()
-            p0 = self.runner._nbt_pending
-            # thread-local capture: the communicator watchdog thread (csrc/bindings/comm_ops.cpp)
-            # keeps polling its events while this thread captures
-            with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                self._graph_stats = self._step_body(self._idx_buf)
-        finally:
-            streams.ENABLED = side_prev
-            if tgt_prev is not None:
-                m.wgrad_block_target_set(tgt_prev)
-        # BN passes of one step, counted on the host (ModelRunner.flush_bn_counters) per replay
-        self._graph_nbt = self.runner._nbt_pending - p0
-        self._graph = g
-        with torch.no_grad():
-            for t, v in zip(state, snap):
-                t.copy_(v)
-        self.runner._nbt_pending = pend
+        with self._training_state_kept():
+            self._host_prelude(1, 0, 1)
+            # The step is captured as ONE chain: the weight gradients run in line on the capture
+            # stream instead of forking to the wgrad side stream (SDX_GRAPH_SIDE=1 keeps the
+            # fork). A captured two-stream DAG replays its branches on several hardware queues
+            # with a cross-queue wait at every fork: 24.9 vs 11.9 ms eager at 256 images/GPU
+            # (23.5 ms even with per-node priorities), while each kernel replayed on its own runs
+            # at its eager speed (profiles/graph_probe_r6.txt, profiles/graph_ab_r6.txt).
+            # In line, the dedicated wgrad kernels get the whole chip (their eager block target
+            # keeps half of it for the concurrent critical path): SDX_GRAPH_WGRAD_BLOCKS, 256.
+            from ..ops import streams
+            side_prev = streams.ENABLED
+            streams.ENABLED = os.environ.get("SDX_GRAPH_SIDE", "0") == "1"
+            m = _ext.require()
+            tgt_prev = m.wgrad_block_target_set(int(os.environ.get("SDX_GRAPH_WGRAD_BLOCKS", "256"))) \
+                if not streams.ENABLED else None
+            try:
+                s = torch.cuda.Stream(device=self.device)
+                s.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(s):
+                    for _ in range(warmup):
+                        self._step_body(self._idx_buf)
+                torch.cuda.current_stream().wait_stream(s)
+                g = torch.cuda.CUDAGraph()
+                p0 = self.runner._nbt_pending
+                # thread-local capture: the communicator watchdog thread (csrc/bindings/comm_ops.cpp)
+                # keeps polling its events while this thread captures
+                with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                    self._graph_stats = self._step_body(self._idx_buf)
+            finally:
+                streams.ENABLED = side_prev
+                if tgt_prev is not None:
+                    m.wgrad_block_target_set(tgt_prev)
+            # BN passes of one step, counted on the host (ModelRunner.flush_bn_counters) per replay
+            self._graph_nbt = self.runner._nbt_pending - p0
+            self._graph = g
         return True
 
     def _norm_terms(self, feats):
@@ -675,7 +357,7 @@ class PretrainEngine:
         x = feats.detach().float().contiguous()
         n_global = float(x.shape[0] * self.world)
         mom = float(self.opt.norm_momentum)
-        sums = getattr(self, "_ns_sums", None)
+        sums = self._ns_sums
         if sums is None or sums.device != x.device:
             sums = self._ns_sums = torch.zeros(2, dtype=torch.float64, device=x.device)
         # nothing in the step reads these: on the wgrad side stream (idle here), off the loss
@@ -711,7 +393,7 @@ class PretrainEngine:
                 # --syncbn_comm auto: measure the transports on this batch (state restored)
                 self.autotune_syncbn(idx)
             data_time.update(time.time() - end)
-            if opt.cuda_graph and self._graph is None and not getattr(self, "_graph_failed", False):
+            if opt.cuda_graph and self._graph is None and not self._graph_failed:
                 try:
                     ok = self.enable_cuda_graph(idx)
                     logging.info("hipGraph capture of the train step: " + ("enabled" if ok else "not applicable"))
@@ -759,31 +441,16 @@ class PretrainEngine:
                 window_n = 0
         # BN num_batches_tracked is host-counted on the native path: visible in the buffers
         # from every epoch end on, not only through state_dict()
-        flush = getattr(self.runner, "flush_bn_counters", None)
-        if flush is not None:
-            flush()
+        self.runner.flush_bn_counters()
         return losses.avg
 
-    def run(self):
-        opt = self.opt
-        for epoch in range(self.start_epoch, opt.epochs + 1):
-            adjust_learning_rate(opt, self.optimizer, epoch)
-            t1 = time.time()
-            loss = self.train_epoch(epoch)
-            t2 = time.time()
-            logging.info("epoch {}, total time {:.2f}".format(epoch, t2 - t1))
-            if self.rank == 0:
-                self.logger.log_value("loss", loss, epoch)
-                self.logger.log_value("learning_rate", self.optimizer.param_groups[0]["lr"], epoch)
-            if self.knn is not None and (epoch % opt.knn_freq == 0 or epoch == opt.epochs):
-                self.knn_eval(epoch)
-            if epoch % opt.save_freq == 0 and self.rank == 0:
-                f = os.path.join(opt.save_folder, f"ckpt_epoch_{epoch}.pth")
-                ckpt_mod.save_model(self.model, self.optimizer, opt, epoch, f, self._extra_state(epoch))
-            comm.barrier()
-        if self.rank == 0:
-            f = os.path.join(opt.save_folder, "last.pth")
-            ckpt_mod.save_model(self.model, self.optimizer, opt, opt.epochs, f, self._extra_state(opt.epochs))
-            self.logger.close()
-        comm.barrier()
-        return os.path.join(opt.save_folder, "last.pth")
+    def _epoch(self, epoch: int) -> dict:
+        t1 = time.time()
+        loss = self.train_epoch(epoch)
+        logging.info("epoch {}, total time {:.2f}".format(epoch, time.time() - t1))
+        return {"loss": loss}
+
+    def _evaluate(self, epoch: int) -> dict:
+        if self.knn is not None and (epoch % self.opt.knn_freq == 0 or epoch == self.opt.epochs):
+            self.knn_eval(epoch)
+        return {}

@@ -24,32 +24,25 @@ load into ``main_linear.py --ckpt`` and the whole ``model`` into ``SupCEResNet``
 """
 from __future__ import annotations
 
+import dataclasses
 import logging
-import os
 import sys
 import time
-from typing import Optional
 
 import numpy as np
 import torch
-import torch.distributed as dist
 
-from ..data.augment import AugConfig, augment, default_resize, nhwc8_to_nchw
-from ..data.datasets import build_dataset
+from ..data.augment import AugConfig
 from ..data.sampler import DistributedIndexSampler, label_subset
-from ..models.executor import ModelRunner
+from ..data.store import probe_stores
 from ..models.resnet import SupCEResNet
-from ..ops import _ext
+from ..ops import _ext, linear_probe
 from ..ops.ce_head import classifier_ce
-from ..optim.flat import FlatParams, build_optimizer
-from ..optim.schedules import adjust_learning_rate, warmup_learning_rate
 from ..parallel import comm
-from ..parallel.ddp import GradBucketReducer
-from ..utils.logging import setup_logging
 from ..utils.meters import AverageMeter
 from ..utils.profiling import PhaseTimer
 from . import checkpoint as ckpt_mod
-from .pretrain import PretrainEngine, _priority_stream, resolve_backend, step_seed
+from .base import TrainEngine
 
 
 def load_encoder(model: torch.nn.Module, path: str):
@@ -64,166 +57,71 @@ def load_encoder(model: torch.nn.Module, path: str):
     return len(enc)
 
 
-class SupervisedEngine(PretrainEngine):
+class SupervisedEngine(TrainEngine):
     """Shares the distributed set-up, SyncBN transports, augmentation call and gradient-buffer
-    zeroing of :class:`PretrainEngine`; the model, the step, validation and logging are its own."""
+    zeroing of :class:`PretrainEngine` through their base :class:`TrainEngine`; the model, the
+    loss, validation and logging are its own."""
 
-    def __init__(self, opt, device: Optional[torch.device] = None):
+    data_first = True       # n_cls comes from the data
+
+    def __init__(self, opt, device=None):
         if getattr(opt, "cuda_graph", False) or getattr(opt, "micro_batch", 0):
             raise ValueError("the supervised trainer supports neither --cuda_graph nor --micro_batch")
-        self.opt = opt
-        rank, local_rank, world, dev = comm.init_distributed(opt.dist_backend, getattr(opt, "comm_timeout", 600.0),
-                                                             device=device)
-        self.rank, self.world, self.device = rank, world, dev
-        self.stream = None
-        if dev.type == "cuda" and os.environ.get("SDX_STREAM_PRIO", "1") != "0":
-            self.stream = _priority_stream(dev)
-            torch.cuda.set_stream(self.stream)
-        if opt.ngpu != world and world > 1:
-            logging.warning(f"--ngpu {opt.ngpu} != launcher WORLD_SIZE {world}; using {world}")
-        opt.world_size = world
-        opt.local_batch = opt.batch_size // world
-        setup_logging(opt.save_folder, rank)
-        if rank == 0:
-            logging.info(f"create {opt.conf_work_path} ...")
-        torch.manual_seed(opt.seed)
-        self.backend = resolve_backend(opt.backend, dev, opt.stem)
+        super().__init__(opt, device)
 
+    def _build_data(self):
         # data: whole uint8 training set resident on the device; an ImageFolder keeps native
         # resolutions (ragged store) for RandomResizedCrop, its validation split the Resize target
-        nw, size = opt.num_workers, opt.size
-        folder = opt.dataset == "path" and not opt.synthetic
-        self.resize = (getattr(opt, "resize", 0) or default_resize(size)) if folder else 0
-        tr = build_dataset(opt.dataset, opt.data_folder, True, opt.synthetic, opt.synthetic_size, size, opt.seed,
-                           native=folder, workers=nw)
-        va = build_dataset(opt.dataset, opt.val_folder if folder else opt.data_folder, False, opt.synthetic,
-                           opt.synthetic_size, size, opt.seed, workers=nw, eval_resize=self.resize)
-        if folder and tr.classes != va.classes:
-            raise ValueError("--val_folder has other classes than --data_folder")
-        if not opt.n_cls:
-            opt.n_cls = max(tr.num_classes, va.num_classes)
-        self.data = torch.from_numpy(tr.images).to(dev)
-        self.data_offs = torch.from_numpy(tr.offsets).to(dev) if tr.ragged else None
-        self.data_hw = torch.from_numpy(tr.sizes).to(dev) if tr.ragged else None
-        self.labels = torch.from_numpy(tr.labels).to(dev)
-        self.va_x, self.va_y = torch.from_numpy(va.images).to(dev), torch.from_numpy(va.labels).to(dev)
-        self.va_offs = torch.from_numpy(va.offsets).to(dev) if va.ragged else None
-        self.va_hw = torch.from_numpy(va.sizes).to(dev) if va.ragged else None
-        self.n_val = len(va)
+        opt = self.opt
+        self.train, self.val, self.resize, self.aug_val, opt.n_cls = probe_stores(opt, self.device)
         # --label_frac: the labelled subset, the same on every rank; the sampler runs over it
-        self._labels_np = np.asarray(tr.labels).astype(np.int64)
+        self._labels_np = self.train.labels.cpu().numpy().astype(np.int64)
         self.subset = label_subset(self._labels_np, opt.label_frac, opt.seed)
         if opt.label_frac < 1.0:
-            logging.info(f"--label_frac {opt.label_frac}: {self.subset.size} of {len(tr)} training images")
-        self.sampler = DistributedIndexSampler(int(self.subset.size), opt.local_batch, world, rank, seed=opt.seed)
+            logging.info(f"--label_frac {opt.label_frac}: {self.subset.size} of {len(self.train)} training images")
+        self.sampler = DistributedIndexSampler(int(self.subset.size), opt.local_batch, self.world, self.rank,
+                                               seed=opt.seed)
         if len(self.sampler) < 1:
             raise ValueError(f"{self.subset.size} training images make no batch of {opt.batch_size}")
         if getattr(opt, "blur_p", 0.0) > 0:
-            import dataclasses
-            self.aug = dataclasses.replace(AugConfig.simclr(size, opt.mean_t, opt.std_t, blur_p=opt.blur_p,
+            self.aug = dataclasses.replace(AugConfig.simclr(opt.size, opt.mean_t, opt.std_t, blur_p=opt.blur_p,
                                                             blur_kernel=opt.blur_kernel, blur_sigma=opt.blur_sigma),
                                            n_views=1)
         else:
-            self.aug = AugConfig.linear_train(size, opt.mean_t, opt.std_t)
-        self.aug_val = (AugConfig.center_crop(size, opt.mean_t, opt.std_t, self.resize) if folder
-                        else AugConfig.evaluation(size, opt.mean_t, opt.std_t))
+            self.aug = AugConfig.linear_train(opt.size, opt.mean_t, opt.std_t)
 
+    def _build_model(self):
+        # fc is part of the flat buffer: SGD / LARS, weight decay and the reducer treat it like
+        # every other parameter
+        opt = self.opt
         model = SupCEResNet(opt.model, opt.n_cls, opt.stem)
         if opt.ckpt:
             n = load_encoder(model, opt.ckpt)
             logging.info(f"fine-tuning: {n} encoder tensors from {opt.ckpt}, fresh classifier")
-        self.sync_group = None
-        if opt.syncBN and world > 1:
-            if self.backend == "torch":
-                from ..parallel.syncbn import convert_sync_bn
-                model = convert_sync_bn(model)
-                self.syncbn_transport = "torch-syncbn"
-            else:
-                self.sync_group = dist.group.WORLD
-                self._setup_syncbn_comm(opt, dev)
-                if self.syncbn_transport == "none":
-                    self.syncbn_transport = "process-group"
-                self._syncbn_pending = False      # (no transport measurement in this trainer)
-        model = model.to(dev)
-        if dev.type == "cuda":
-            model = model.to(memory_format=torch.channels_last)
-        self.model = model
-        # fc is part of the flat buffer: SGD / LARS, weight decay and the reducer treat it like
-        # every other parameter
-        self.flat = FlatParams(model)
-        self.optimizer = build_optimizer(opt.optimizer, self.flat, opt.learning_rate, opt.momentum,
-                                         opt.weight_decay, backend="torch" if self.backend == "torch" else "auto")
-        self.reducer = (GradBucketReducer(self.flat, compress=getattr(opt, "grad_compress", "none"))
-                        if world > 1 else None)
-        self.optimizer.grad_scale = 1.0 / world
-        self.runner = ModelRunner(model, self.backend, opt.precision, self.sync_group, master=self.flat.flat)
-        self.logger = None
-        if rank == 0:
-            from ..utils.tb import Logger
-            self.logger = Logger(opt.tb_folder, flush_secs=2)
-        self.start_epoch = 1
-        self.global_step = 0
-        self._seed_t = torch.zeros((1,), dtype=torch.int64, device=dev)
-        self._seed_host = 0
-        self._seed_dev = False
-        self.prof = PhaseTimer(getattr(opt, "profile", False), dev)
-        self.knn = None
-        self.history = []          # one dict per finished epoch (train / validation figures)
-        if getattr(opt, "resume", ""):
-            self._resume(opt.resume)
+        return model
 
-    def _resume(self, path):
-        st = ckpt_mod.load_checkpoint(path)
-        ckpt_mod.load_model_state(self.model, st["model"])
-        self.optimizer.load_state_dict(st["optimizer"])
-        self.start_epoch = int(st["epoch"]) + 1
-        self.global_step = int((st.get("sdx_state") or {}).get("global_step", 0))
-        logging.info(f"resumed from {path} at epoch {self.start_epoch}")
+    def _init_state(self):
+        self._syncbn_pending = False      # (no transport measurement in this trainer)
+        self.history = []          # one dict per finished epoch (train / validation figures)
 
     def _extra_state(self, epoch):
-        return {"global_step": self.global_step, "epoch": epoch, "n_cls": int(self.opt.n_cls),
-                "label_frac": float(self.opt.label_frac)}
+        return dict(super()._extra_state(epoch), n_cls=int(self.opt.n_cls), label_frac=float(self.opt.label_frac))
 
     # ------------------------------------------------------------------------------
-    def _host_prelude(self, epoch: int, it: int, iters: int):
-        warmup_learning_rate(self.opt, epoch, it, iters, self.optimizer)
-        self.optimizer._sync_lr()
-        self._seed_host = step_seed(self.opt.seed, epoch, it, self.rank)
-
     def _step_body(self, idx: torch.Tensor, labels: torch.Tensor, epoch: int = 1, it: int = 0):
         """Device work of one step: no host synchronisation."""
         ph = self.prof.phase
         with ph("augment"):
-            prefetch = getattr(self.runner, "prefetch_weights", None)
-            if prefetch is not None:
-                prefetch()
-            zeroed = self._zero_grad_side()
-            x = self.make_views(idx, epoch, it)
+            zeroed, x = self._start_step(idx, epoch, it)
         with ph("forward"):
             feat = self.runner.encode(x)
         with ph("loss"):
             loss, stats = classifier_ce(feat, self.model.fc, labels, native=self.backend == "native")
-        with ph("backward"):
-            if zeroed is not None:
-                torch.cuda.current_stream(self.device).wait_event(zeroed)
-            else:
-                self.optimizer.zero_grad()
-            one = getattr(self, "_one_grad", None)
-            if one is None or one.device != loss.device or one.dtype != loss.dtype:
-                one = self._one_grad = torch.ones((), device=loss.device, dtype=loss.dtype)
-            loss.backward(one)
-        if self.reducer is not None:
-            with ph("grad_sync_wait"):
-                self.reducer.finish()
-        with ph("optimizer"):
-            self.optimizer.step()
+        self._backward_and_update(loss, zeroed)
         return {"loss_local": loss.detach(), "stats": stats}
 
     def train_step(self, idx: torch.Tensor, labels: torch.Tensor, epoch: int, it: int, iters: int):
-        self._host_prelude(epoch, it, iters)
-        st = self._step_body(idx, labels, epoch, it)
-        self.global_step += 1
-        return st
+        return self._train_step((idx, labels), epoch, it, iters)
 
     def epoch_batches(self, epoch: int):
         """(dataset indices, labels) of this rank's batches of ``epoch``: the sampler's
@@ -281,9 +179,7 @@ class SupervisedEngine(PretrainEngine):
                     sys.stdout.flush()
                 win = torch.zeros(3, device=self.device)
                 win_n = 0
-        flush = getattr(self.runner, "flush_bn_counters", None)
-        if flush is not None:
-            flush()
+        self.runner.flush_bn_counters()
         return losses.avg, top1.avg
 
     # ------------------------------------------------------------------------------
@@ -291,69 +187,44 @@ class SupervisedEngine(PretrainEngine):
     def validate(self):
         """(loss, top-1, top-5) of the current model on the validation split, eval-mode BatchNorm.
         Every rank evaluates the whole split (the replicas are identical)."""
-        opt = self.opt
-        was_training = self.model.training
-        self.model.eval()
         fc = self.model.fc
         native = self.backend == "native"
-        folded = None
-        if native:
-            from ..ops import linear_probe
-            folded = linear_probe.FoldedEncoder(self.model.encoder)    # the weights of NOW
-            native_ce = linear_probe.supported(self.model)
+        encode, restore = linear_probe.eval_encoder(self.model, self.backend, self.runner)   # the weights of NOW
+        native_ce = native and linear_probe.supported(self.model)
         tot = torch.zeros(3, dtype=torch.float64, device=self.device)
-        n, vb = self.n_val, opt.val_batch_size
+        n, vb = len(self.val), self.opt.val_batch_size
         for s in range(0, n, vb):
             idx = torch.arange(s, min(s + vb, n), device=self.device)
-            x = augment(self.va_x, idx, self.aug_val, 0, self.va_offs, self.va_hw)
-            labels = self.va_y[idx]
-            if native:
-                feat = folded(x)
-                if native_ce:
-                    st = _ext.require().linear_ce_step(feat.float().contiguous(), fc.weight.data, fc.bias.data,
-                                                       labels.long(), None, None, 0.0, 0.0, 0.0, False, False)[1]
-                else:
-                    st = classifier_ce(feat, fc, labels, native=False)[1]
+            x = self.val.views(idx, self.aug_val, 0)
+            labels = self.val.labels[idx]
+            feat = encode(x)
+            if native_ce:
+                st = _ext.require().linear_ce_step(feat.float().contiguous(), fc.weight.data, fc.bias.data,
+                                                   labels.long(), None, None, 0.0, 0.0, 0.0, False, False)[1]
             else:
-                feat = self.runner.encode(nhwc8_to_nchw(x), training=False).float()
                 st = classifier_ce(feat, fc, labels, native=False)[1]
             tot += st.double()
+        restore()
         v = tot.tolist()
-        self.model.train(was_training)
         loss, acc1, acc5 = v[0] / n, 100.0 * v[1] / n, 100.0 * v[2] / n
         logging.info(" * Acc@1 {:.3f}, Acc@5 {:.3f}, loss {:.4f}".format(acc1, acc5, loss))
         return loss, acc1, acc5
 
-    def run(self):
-        opt = self.opt
-        best_acc = 0.0
-        for epoch in range(self.start_epoch, opt.epochs + 1):
-            adjust_learning_rate(opt, self.optimizer, epoch)
-            t1 = time.time()
-            loss, acc = self.train_epoch(epoch)
-            logging.info("Train epoch {}, total time {:.2f}, accuracy:{:.2f}".format(epoch, time.time() - t1, acc))
-            rec = {"epoch": epoch, "train_loss": loss, "train_acc": acc}
-            if self.rank == 0:
-                self.logger.log_value("train_loss", loss, epoch)
-                self.logger.log_value("train_acc", acc, epoch)
-                self.logger.log_value("learning_rate", self.optimizer.param_groups[0]["lr"], epoch)
-            if epoch % opt.val_freq == 0 or epoch == opt.epochs:
-                vloss, vacc, vacc5 = self.validate()
-                rec.update(val_loss=vloss, val_acc=vacc, val_acc5=vacc5)
-                best_acc = max(best_acc, vacc)
-                if self.rank == 0:
-                    self.logger.log_value("val_loss", vloss, epoch)
-                    self.logger.log_value("val_acc", vacc, epoch)
-                    self.logger.log_value("val_acc5", vacc5, epoch)
-            self.history.append(rec)
-            if epoch % opt.save_freq == 0 and self.rank == 0:
-                f = os.path.join(opt.save_folder, f"ckpt_epoch_{epoch}.pth")
-                ckpt_mod.save_model(self.model, self.optimizer, opt, epoch, f, self._extra_state(epoch))
-            comm.barrier()
-        logging.info("best accuracy: {:.2f}".format(best_acc))
-        if self.rank == 0:
-            f = os.path.join(opt.save_folder, "last.pth")
-            ckpt_mod.save_model(self.model, self.optimizer, opt, opt.epochs, f, self._extra_state(opt.epochs))
-            self.logger.close()
-        comm.barrier()
-        return os.path.join(opt.save_folder, "last.pth")
+    def _epoch(self, epoch: int) -> dict:
+        t1 = time.time()
+        loss, acc = self.train_epoch(epoch)
+        logging.info("Train epoch {}, total time {:.2f}, accuracy:{:.2f}".format(epoch, time.time() - t1, acc))
+        self.history.append({"epoch": epoch, "train_loss": loss, "train_acc": acc})
+        return {"train_loss": loss, "train_acc": acc}
+
+    def _evaluate(self, epoch: int) -> dict:
+        if not (epoch % self.opt.val_freq == 0 or epoch == self.opt.epochs):
+            return {}
+        vloss, vacc, vacc5 = self.validate()
+        rec = {"val_loss": vloss, "val_acc": vacc, "val_acc5": vacc5}
+        self.history[-1].update(rec)
+        return rec
+
+    def _end_of_run(self):
+        best = max((h.get("val_acc", 0.0) for h in self.history), default=0.0)
+        logging.info("best accuracy: {:.2f}".format(best))

@@ -82,6 +82,30 @@ class FoldedEncoder:
         return global_avgpool_nhwc(out)
 
 
+def eval_encoder(model: torch.nn.Module, backend: str, runner=None):
+    """(encode, restore): ``encode`` maps an NHWC batch (data/augment.py) to the fp32 features of
+    ``model.encoder`` in eval mode, ``restore`` undoes what that had to set. native: a
+    :class:`FoldedEncoder` of the weights and statistics of NOW (a caller whose encoder trains
+    asks again at every evaluation), nothing to restore; torch: ``runner.encode`` after the
+    encoder's ``training`` flags were recorded and ``eval()`` set."""
+    if backend == "native":
+        return FoldedEncoder(model.encoder), (lambda: None)
+    from ..data.augment import nhwc8_to_nchw
+    enc = model.encoder
+    flags = [(m, m.training) for m in enc.modules()]
+    enc.eval()
+
+    def restore():
+        for m, t in flags:
+            m.training = t
+
+    @torch.no_grad()
+    def encode(x):
+        return runner.encode(nhwc8_to_nchw(x), training=False).float()
+
+    return encode, restore
+
+
 class NativeLinearCE:
     """``LinearClassifier`` trained with cross-entropy and SGD on the native path. Holds its
     own momentum buffers (the linear probe writes no checkpoint, main_linear.py)."""

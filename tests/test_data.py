@@ -82,7 +82,7 @@ def test_engine_step_image_folder_cpu_aug(tmp_path, gpu_aug):
                           "--size", "16", "--batch_size", "4", "--gpu_aug", str(gpu_aug), "--num_workers", "2",
                           "--work_dir", str(tmp_path / "ws")], make_dirs=False)
     eng = PretrainEngine(opt)
-    assert eng.data_offs is not None and eng.data.dim() == 1
+    assert eng.train.offs is not None and eng.train.images.dim() == 1
     st = eng.train_step(torch.arange(4), 1, 0, 2)
     assert torch.isfinite(st["loss_local"])
 

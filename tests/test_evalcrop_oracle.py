@@ -284,9 +284,9 @@ def test_linear_engine_on_an_image_folder(tmp_path):
     eng = LinearEngine(opt, device=torch.device("cpu"))
     assert opt.n_cls == 3 and eng.classifier.fc.out_features == 3
     assert eng.aug_val.resize == 37 and eng.aug_val.size == 32 and eng.aug_train.resize == 0 and eng.aug_train.crop
-    assert eng.tr_offs is not None and eng.va_offs is not None and eng.n_val == 12
-    assert int(eng.va_hw.min()) <= 37        # the validation store is capped at the Resize target
-    assert int(eng.va_hw.min(dim=1).values.max()) <= 37
+    assert eng.train.offs is not None and eng.val.offs is not None and len(eng.val) == 12
+    assert int(eng.val.hw.min()) <= 37        # the validation store is capped at the Resize target
+    assert int(eng.val.hw.min(dim=1).values.max()) <= 37
     logged = {}
     log_value = eng.logger.log_value
 
@@ -315,9 +315,9 @@ def test_pretrain_knn_bank_is_the_resident_store(tmp_path):
     eng = PretrainEngine(opt, device=torch.device("cpu"))
     ev = eng.knn
     assert ev is not None and ev.n_cls == 3 and ev.aug.resize == 37
-    assert ev.bank_x is eng.data and ev.bank_x.untyped_storage().data_ptr() == eng.data.untyped_storage().data_ptr()
-    assert ev._ragged[id(ev.bank_x)][0] is eng.data_offs and ev._ragged[id(ev.val_x)][0] is not None
-    assert ev._count(ev.bank_x) == 24 and ev._count(ev.val_x) == 12
+    assert ev.bank is eng.train and ev.bank.images.untyped_storage().data_ptr() == eng.train.images.untyped_storage().data_ptr()
+    assert ev.bank.offs is eng.train.offs and ev.val.offs is not None
+    assert len(ev.bank) == 24 and len(ev.val) == 12
     from simclr_pytorch_distributed_amd.utils.tb import read_events
     path = eng.logger.path
     eng.run()
@@ -328,7 +328,7 @@ def test_pretrain_knn_bank_is_the_resident_store(tmp_path):
     acc5 = [(s, v) for s, t, v in events if t == "knn/val_acc5"]
     assert [s for s, _ in acc1] == [1] and 0.0 <= acc1[0][1] <= 100.0
     assert [v for _, v in acc5] == [100.0]      # 3 classes: top-5 always hits
-    assert ev.bank_x is eng.data
+    assert ev.bank is eng.train
     # without --val_folder the ragged store still refuses
     opt.val_folder = None
     with pytest.raises(ValueError, match="val_folder"):

@@ -155,10 +155,10 @@ def test_cuda_graph_replays_draw_fresh_blurred_views(gpu, tmp_path):
         torch.cuda.synchronize()
         assert len(seen) == n_calls, "the step was not replayed from the graph"
         views.append(static.clone())
-        eager = gpu_augment(eng.data, idx, eng.aug, eng._seed_host, offs=eng.data_offs, hw=eng.data_hw)
+        eager = gpu_augment(eng.train.images, idx, eng.aug, eng._seed_host, offs=eng.train.offs, hw=eng.train.hw)
         assert torch.equal(views[-1].view(torch.int16), eager.view(torch.int16)), it
-        plain = gpu_augment(eng.data, idx, dataclasses.replace(eng.aug, blur_p=0.0), eng._seed_host,
-                            offs=eng.data_offs, hw=eng.data_hw)
+        plain = gpu_augment(eng.train.images, idx, dataclasses.replace(eng.aug, blur_p=0.0), eng._seed_host,
+                            offs=eng.train.offs, hw=eng.train.hw)
         same = [torch.equal(eager[i].view(torch.int16), plain[i].view(torch.int16)) for i in range(16)]
         assert 0 < sum(same) < 16, (it, same)      # blurred and un-blurred views in the batch
     assert not torch.equal(views[0].view(torch.int16), views[1].view(torch.int16))

@@ -145,18 +145,16 @@ def test_linear_engine_native_on_an_image_folder(gpu, tmp_path):
                         "--work_dir", str(tmp_path / "ws")])
     eng = LinearEngine(opt, device=gpu)
     assert eng.backend == "native" and eng.folded is not None and opt.n_cls == 3
-    assert eng.aug_val.resize == 37 and eng.va_offs is not None and eng.tr_offs is not None
+    assert eng.aug_val.resize == 37 and eng.val.offs is not None and eng.train.offs is not None
     loss, a1, a5 = eng.train_epoch(1)
     vl, v1, v5 = eng.validate()
     k1, k5 = eng.knn_eval()
     assert all(math.isfinite(v) for v in (loss, a1, a5, vl, v1, v5, k1, k5))
     assert 0.0 <= a1 <= 100.0 and 0.0 <= v1 <= v5 <= 100.0 and 0.0 <= k1 <= k5 <= 100.0
-    ev = KnnEvaluator(eng.model, "native", "bf16", eng.tr_x, eng.tr_y, eng.va_x, eng.va_y, opt.mean_t, opt.std_t, 32,
-                      3, k=5, bank_offs=eng.tr_offs, bank_hw=eng.tr_hw, val_offs=eng.va_offs, val_hw=eng.va_hw,
-                      resize=eng.resize)
-    got = ev.extract(eng.va_x)
+    ev = KnnEvaluator(eng.model, "native", "bf16", eng.train, eng.val, eng.aug_val, 3, k=5)
+    got = ev.extract(eng.val)
     assert tuple(got.shape) == (12, 512) and torch.isfinite(got).all()
-    twin = augment_reference(eng.va_x, torch.arange(12), eng.aug_val, 0, eng.va_offs, eng.va_hw)
+    twin = augment_reference(eng.val.images, torch.arange(12), eng.aug_val, 0, eng.val.offs, eng.val.hw)
     x = nhwc8_to_nchw(twin).to(torch.bfloat16).float().to(gpu)
     with torch.no_grad():
         ref = F.normalize(eng.model.encoder(x).float(), dim=1)

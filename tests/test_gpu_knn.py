@@ -163,6 +163,7 @@ def _synthetic(gpu, n_bank=256, n_val=128):
 @pytest.mark.parametrize("name", ["resnet18", "resnet50"])
 def test_evaluator_native(gpu, name):
     from simclr_pytorch_distributed_amd.data.augment import AugConfig, augment
+    from simclr_pytorch_distributed_amd.data.store import DeviceStore
     from simclr_pytorch_distributed_amd.engine.knn import KnnEvaluator
     from simclr_pytorch_distributed_amd.models.resnet import SupConResNet
     from simclr_pytorch_distributed_amd.ops.linear_probe import FoldedEncoder
@@ -170,7 +171,9 @@ def test_evaluator_native(gpu, name):
     model = SupConResNet(name).to(gpu).to(memory_format=torch.channels_last)
     model.train()
     bx, by, vx, vy = _synthetic(gpu)
-    ev = KnnEvaluator(model, "native", "bf16", bx, by, vx, vy, MEAN, STD, 32, 10, k=200, T=0.1, batch_size=128)
+    bank = DeviceStore(bx, by)
+    ev = KnnEvaluator(model, "native", "bf16", bank, DeviceStore(vx, vy), AugConfig.evaluation(32, MEAN, STD), 10,
+                      k=200, T=0.1, batch_size=128)
     before = {k: v.clone() for k, v in model.state_dict().items()}
     top1, top5 = ev.evaluate()
     assert 0.0 <= top1 <= top5 <= 100.0
@@ -179,7 +182,7 @@ def test_evaluator_native(gpu, name):
     direct = F.normalize(FoldedEncoder(model.encoder)(x).float(), dim=1)
     assert ev.last_bank.shape == (256, 512 if name == "resnet18" else 2048)
     assert torch.equal(ev.last_bank[:128], direct)
-    assert torch.equal(ev.extract(bx, 0, 128), direct)
+    assert torch.equal(ev.extract(bank, 0, 128), direct)
 
 
 def test_evaluate_leaves_training_undisturbed(gpu, tmp_path):

@@ -39,7 +39,7 @@ def test_one_step_parity(gpu, tmp_path):
         eng.model.train()
         eng.aug = AugConfig.evaluation(32, eng.opt.mean_t, eng.opt.std_t)
         idx = torch.arange(16, device=gpu)
-        st = eng.train_step(idx, eng.labels[idx], 1, 0, 1)
+        st = eng.train_step(idx, eng.train.labels[idx], 1, 0, 1)
         torch.cuda.synchronize()
         params = dict(eng.model.named_parameters())
         res[tag] = {"loss": st["loss_local"].double().reshape(1).clone(),
@@ -76,10 +76,10 @@ def test_train_checkpoint_resume(gpu, tmp_path):
     m = SupCEResNet("resnet18", 10)
     ckpt_mod.load_model_state(m, st["model"])                  # strict: every key, nothing else
     m = m.to(gpu).eval()
-    n = eng.n_val
+    n = len(eng.val)
     with torch.no_grad():
-        x = augment(eng.va_x, torch.arange(n, device=gpu), AugConfig.evaluation(32, opt.mean_t, opt.std_t), 0)
-        hits_t = int((m(nhwc8_to_nchw(x).float()).argmax(1) == eng.va_y).sum())
+        x = augment(eng.val.images, torch.arange(n, device=gpu), AugConfig.evaluation(32, opt.mean_t, opt.std_t), 0)
+        hits_t = int((m(nhwc8_to_nchw(x).float()).argmax(1) == eng.val.labels).sum())
     _, acc1, _ = eng.validate()
     hits_n = acc1 * n / 100.0
     print(f"validation top-1 hits: native {hits_n:.1f}, torch eval of the reloaded model {hits_t} (of {n})")

@@ -102,13 +102,16 @@ def _synthetic(n_bank=64, n_val=32):
 
 
 def _evaluator(n_bank=64, n_val=32, k=20):
+    from simclr_pytorch_distributed_amd.data.augment import AugConfig
+    from simclr_pytorch_distributed_amd.data.store import DeviceStore
     from simclr_pytorch_distributed_amd.engine.knn import KnnEvaluator
     from simclr_pytorch_distributed_amd.models.resnet import SupConResNet
     torch.manual_seed(0)
     model = SupConResNet("resnet18", "mlp", 128, "cifar")
     model.train()
     bx, by, vx, vy = _synthetic(n_bank, n_val)
-    return model, KnnEvaluator(model, "torch", "fp32", bx, by, vx, vy, MEAN, STD, 32, 10, k=k, T=0.1, batch_size=32)
+    return model, KnnEvaluator(model, "torch", "fp32", DeviceStore(bx, by), DeviceStore(vx, vy),
+                               AugConfig.evaluation(32, MEAN, STD), 10, k=k, T=0.1, batch_size=32)
 
 
 def test_evaluator_cpu_has_no_side_effects():
@@ -164,9 +167,9 @@ def test_two_gloo_ranks_equal_single_process():
 
 
 def _tiny_run(tmp_path, knn_freq, monkeypatch):
-    from simclr_pytorch_distributed_amd.engine import pretrain
+    from simclr_pytorch_distributed_amd.data import store
     from simclr_pytorch_distributed_amd.engine.pretrain import PretrainEngine
-    real = pretrain.build_dataset
+    real = store.build_dataset
 
     def small_val(dataset, folder, train=True, synthetic=False, synthetic_size=50000, *a, **k):
         # the synthetic validation split has at least 1000 images; 32 are enough to see the tags
@@ -175,7 +178,7 @@ def _tiny_run(tmp_path, knn_freq, monkeypatch):
             ds.images, ds.labels = ds.images[:32], ds.labels[:32]
         return ds
 
-    monkeypatch.setattr(pretrain, "build_dataset", small_val)
+    monkeypatch.setattr(store, "build_dataset", small_val)
     from simclr_pytorch_distributed_amd.utils.tb import read_events
     opt = parse_pretrain(["--model", "resnet18", "--batch_size", "8", "--synthetic", "--synthetic_size", "32",
                           "--epochs", "2", "--max_steps", "1", "--backend", "torch", "--precision", "fp32",

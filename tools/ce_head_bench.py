@@ -94,7 +94,7 @@ def step(a):
     sup.model.train()
     sim.model.train()
     idx = torch.arange(a.images, device=dev)
-    labels = sup.labels[idx]
+    labels = sup.train.labels[idx]
     variants = [(f"supervised CE step, {a.images} images", lambda: sup.train_step(idx, labels, 1, 0, 10)),
                 (f"SimCLR step, {2 * a.images} views", lambda: sim.train_step(idx, 1, 0, 10))]
     r = timed(variants, a.rounds, a.iters)

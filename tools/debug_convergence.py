@@ -16,7 +16,7 @@ import torch
 
 def run(variant, steps, every, seed=0):
     from simclr_pytorch_distributed_amd.config import parse_pretrain
-    from simclr_pytorch_distributed_amd.data.augment import augment, nhwc8_to_nchw
+    from simclr_pytorch_distributed_amd.data.augment import nhwc8_to_nchw
     from simclr_pytorch_distributed_amd.engine.pretrain import PretrainEngine, step_seed
     from simclr_pytorch_distributed_amd.losses.supcon import DistributedContrastiveLoss
     from simclr_pytorch_distributed_amd.models.executor import ModelRunner
@@ -46,7 +46,7 @@ def run(variant, steps, every, seed=0):
         mv = eng.make_views
         eng.make_views = lambda idx, e=1, it=0: nhwc8_to_nchw(mv(idx, e, it))
     elif variant == "aug_torch":
-        eng.make_views = lambda idx, e=1, it=0: augment(eng.data, idx, eng.aug, step_seed(seed, e, it, 0))
+        eng.make_views = lambda idx, e=1, it=0: eng.train.views(idx, eng.aug, step_seed(seed, e, it, 0))
     eng.model.train()
     iters = len(eng.sampler)
     out = []
