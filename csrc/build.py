@@ -61,15 +61,32 @@ def _sources():
     return kern, bind
 
 
+COMMON = ["-std=c++17", "-fPIC", f"-I{os.path.join(CSRC, 'include')}", "-Wno-unused-result",
+          "-Wno-deprecated-declarations"]
+
+
+def kernel_flags(src: str, debug: bool = False, checked: bool = False, defines: list | None = None) -> list:
+    """The hipcc command (up to ``-c src -o obj``) of one ``csrc/kernels`` unit; ``tools/isa_digest.py``
+    compiles with the same."""
+    flags = [_hipcc(), "-x", "hip", f"--offload-arch={ARCH}", "-munsafe-fp-atomics", "-ffp-contract=fast"] + \
+        (["-O0", "-g"] if debug else ["-O3"]) + COMMON + (["-DSDX_CHECKED=1"] if checked else []) + \
+        [f"-D{d}" for d in (defines or [])]
+    # the units of igemm_kernel.h (igemm*.hip): MFMA accumulators in arch VGPRs. The 4-wave 64x128
+    # wave tiles (cfgs 7/8) hold 128 fp32 accumulators per lane; with the default AGPR heuristics
+    # hipcc copied them through a temporary around every MFMA (~600 v_accvgpr moves per kernel); the
+    # VGPR form needs 256 VGPRs + 20 AGPRs and no copies. Every other instantiation compiles to the
+    # same code.
+    if os.path.basename(src).startswith("igemm"):
+        flags += ["-mllvm", "--amdgpu-mfma-vgpr-form"]
+    return flags
+
+
 def build(force: bool = False, jobs: int | None = None, debug: bool = False, verbose: bool = False,
           checked: bool = False, variant: str = "", defines: list | None = None, sanitize: bool = False) -> str:
     os.makedirs(OBJ_DIR, exist_ok=True)
     inc_torch, lib_torch, abi = _torch_paths()
     hipcc = _hipcc()
     py_inc = sysconfig.get_paths()["include"]
-    opt = ["-O0", "-g"] if debug else ["-O3"]
-    common = ["-std=c++17", "-fPIC", f"-I{os.path.join(CSRC, 'include')}", "-Wno-unused-result",
-              "-Wno-deprecated-declarations"]
     # variant: an experiment build _C_<variant>.so with extra kernel defines (loaded with
     # SDX_EXT_VARIANT=<variant>), e.g. --variant fragpin --define SDX_FRAG_PIN=1
     # sanitize: _C_san.so, the host binding layer (csrc/bindings) built with AddressSanitizer
@@ -80,13 +97,10 @@ def build(force: bool = False, jobs: int | None = None, debug: bool = False, ver
         variant = "san"
     name = "_C_checked" if checked else ("_C_" + variant if variant else "_C")
     out_so = os.path.join(PKG, name + ".so")
-    kflags = [hipcc, "-x", "hip", f"--offload-arch={ARCH}", "-munsafe-fp-atomics",
-              "-ffp-contract=fast"] + opt + common + (["-DSDX_CHECKED=1"] if checked else []) + \
-        [f"-D{d}" for d in (defines or [])]
     bflags = [os.environ.get("CXX", "g++"), "-O2", "-D__HIP_PLATFORM_AMD__=1", "-DUSE_ROCM=1",
               "-I/opt/rocm/include",
               f"-D_GLIBCXX_USE_CXX11_ABI={abi}", "-DTORCH_API_INCLUDE_EXTENSION_H",
-              f"-DTORCH_EXTENSION_NAME={name}", f"-I{py_inc}"] + [f"-I{p}" for p in inc_torch] + common + \
+              f"-DTORCH_EXTENSION_NAME={name}", f"-I{py_inc}"] + [f"-I{p}" for p in inc_torch] + COMMON + \
         (SAN_FLAGS if sanitize else [])
     kern, bind = _sources()
 
@@ -114,12 +128,7 @@ def build(force: bool = False, jobs: int | None = None, debug: bool = False, ver
             raise RuntimeError(f"compile failed: {src}\n{r.stdout}\n{r.stderr}")
         return obj, True
 
-    # igemm.hip: MFMA accumulators in arch VGPRs. Its 4-wave 64x128 wave tiles (cfgs 7/8) hold
-    # 128 fp32 accumulators per lane; with the default AGPR heuristics hipcc copied them through
-    # a temporary around every MFMA (~600 v_accvgpr moves per kernel); the VGPR form needs 256
-    # VGPRs + 20 AGPRs and no copies. Every other instantiation compiles to the same code.
-    per_file = {"igemm.hip": ["-mllvm", "--amdgpu-mfma-vgpr-form"]}
-    tasks = [(s, kflags + per_file.get(os.path.basename(s), [])) for s in kern] + [(s, bflags) for s in bind]
+    tasks = [(s, kernel_flags(s, debug, checked, defines)) for s in kern] + [(s, bflags) for s in bind]
     n = jobs or min(8, os.cpu_count() or 4)
     with ThreadPoolExecutor(max_workers=n) as ex:
         results = list(ex.map(lambda t: job(*t), tasks))

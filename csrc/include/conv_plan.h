@@ -1,4 +1,4 @@
-// Host-side dispatch planning of the convolution kernels (igemm.hip, wgrad1x1.hip,
+// Host-side dispatch planning of the convolution kernels (igemm.hip / igemm_kernel.h, wgrad1x1.hip,
 // wgrad3x3.hip): which tile config, main loop and kernel variant a conv pass runs, its split
 // counts, statistics-slab rows and workspace sizes, and every run-time switch that moves
 // them. Plain C++ (no HIP, no torch), header-only like knn_plan.h: the kernel translation
@@ -141,7 +141,7 @@ inline int tap_depth(int64_t cfg) { return cfg == 11 ? 8 : 7; }
 // channels; BM = 128: 8 images of 4x4 = 8·6·6 pixels = 36 KiB)
 constexpr int tap_halo_kb(int bm) { return bm == 256 ? 50 : 36; }
 
-// what launch_tap copies into the kernel parameters (IgemmParams t_*, igemm.hip)
+// what launch_tap copies into the kernel parameters (IgemmParams t_*, igemm_kernel.h)
 struct TapGeom {
   int t_rw, t_rs, t_imgs, t_is, t_hp, t_nhp, t_ky, t_nch;
 };
@@ -289,7 +289,7 @@ inline int conv_cfg(const ConvGeom& g, int cdim, int ncol, int64_t M, int64_t Kd
   return cfg;
 }
 
-// ---- main loop of a fwd / dgrad launch (the template dispatch stays in igemm.hip) ----------
+// ---- main loop of a fwd / dgrad launch (the template dispatch stays in igemm_kernel.h) ----------
 // K-concatenated dgrad [dy | a2]·[Wd ; Mx] (BN3 fold): a stride-1 unpadded 1x1 whose dy
 // width is a power-of-two multiple of a2's (both multiples of BK), on the LDS-DMA loops
 inline bool dgrad_cat_supported(const ConvGeom& g, int cat_ch, const Knobs& k) {

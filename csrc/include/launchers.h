@@ -73,7 +73,7 @@ int bnfold_colsum_blocks();
 hipError_t launch_bnfold_rowdot(const float* G, const void* w, int C, int K, int ns, float* out_rows, hipStream_t s);
 hipError_t launch_bnfold_colsum(const void* x, long rows, int K, float* partial, float* cs, hipStream_t s);
 
-// ---- implicit-GEMM convolution (igemm.hip) ------------------------------------
+// ---- implicit-GEMM convolution (igemm.hip; kernel: igemm_kernel.h, igemm_*.hip) -
 // (ConvGeom and every dispatch decision — tile config, main loop, splits, slab rows — live in
 // conv_plan.h; the launchers below take the plan or call the same plan functions)
 // DGRAD epilogue BatchNorm-backward statistics of the stored dx (= the output gradient of
@@ -119,6 +119,7 @@ struct GemmEpi {
   const float* bias_pre;
 };
 // diagnostic main-loop timeline (SDX_IGEMM_TRACE=1): block 0, waves 0 and 4, s_memtime stamps
+// of the last traced launch (each igemm_*.hip unit has a buffer; igemm.hip picks the unit)
 int igemm_trace_slots();
 hipError_t igemm_trace_copy(unsigned long long* host, hipStream_t s);
 // in_scale/in_shift (optional, [C] fp32): fused BN+ReLU prologue on the input activation
@@ -143,7 +144,7 @@ hipError_t launch_conv_dgrad_merged(const ConvGeom& g, const sdx_plan::DgradPlan
 hipError_t launch_conv_wgrad(const ConvGeom& g, const sdx_plan::WgradPlan& plan, const void* dy, const void* x,
                              float* partial, float* dw, int accumulate, hipStream_t s,
                              const float* in_scale = nullptr, const float* in_shift = nullptr);
-// dW (+)= Σ_split partial[split] (fp32 [splits][n4*4]), deterministic order
+// dW (+)= Σ_split partial[split] (fp32 [splits][n4*4]), deterministic order (splitk.hip)
 hipError_t launch_splitk_reduce(const float* partial, int splits, long n4, float* dw, int accumulate, hipStream_t s);
 // Deferral of the split-K reductions launched on stream s (this host thread): they are queued
 // until splitk_flush(), which issues them as one multi-tensor launch on s. The caller keeps

@@ -3,17 +3,17 @@
 //   dW[k][c] = Σ_pixels dy[p][k] · x[p][c]
 //
 // A plain GEMM whose reduction runs over pixels, so both operands are K-outer (the pixel is
-// the slow dimension of dy and x). The generic implicit-GEMM wgrad (igemm.hip MODE_WGRAD,
+// the slow dimension of dy and x). The generic implicit-GEMM wgrad (igemm_wgrad.hip,
 // 4 waves, one K-tile of register prefetch) runs these at ~450 TFLOP/s with ~4 VALU per
 // MFMA; this kernel is the tap-reuse 3x3 kernel's (wgrad3x3.hip) schedule applied to the
 // 1x1 case: 8 waves (2 x 4) over a 128 x BN output tile, 32-pixel steps, operand loads
 // FOUR steps ahead through a branch-free register ring (base + step·stride addressing, tail
 // steps read the zero page), step-invariant fragment offsets, and one wave of ~256 blocks.
 //
-// LDS images are [32 pixels][COLS] bf16 with igemm.hip's K-outer chunk swizzle for
+// LDS images are [32 pixels][COLS] bf16 with the K-outer chunk swizzle of mfma_lds.h for
 // COLS >= 128 (row & 3, bit 3 of the row), read with ds_read_b64_tr_b16. The MFMA is issued
 // as D = Bᵀ·Aᵀ (each lane holds 4 consecutive output columns of one output row). Output: an
-// fp32 partial slab per K-split, reduced deterministically by igemm.hip's split-K reduction.
+// fp32 partial slab per K-split, reduced deterministically by the split-K reduction (splitk.hip).
 //
 // Shapes: K % 128 == 0, C % BN == 0 (BN = 256, or 128 when C is not a multiple of 256),
 // N·P·Q % 32 == 0 — layers 2-4 of the CIFAR/ImageNet ResNet bottlenecks (reference
@@ -26,6 +26,7 @@
 
 #include "common.h"
 #include "launchers.h"
+#include "mfma_lds.h"
 
 using namespace sdx;
 
@@ -42,21 +43,12 @@ constexpr int W1_NT = 512;      // 8 waves: 2 (output rows) x 4 (output columns)
 constexpr int W1_BM = 128;      // output channels (dW rows) per block
 constexpr int W1_PF = 4;        // steps of loads in flight (register ring of 4 named slots)
 
-typedef __attribute__((address_space(3))) bf16x4 w1_lds_bf16x4;
-
-__device__ __attribute__((aligned(16))) uint16_t w1_zero16[8];
-typedef const __attribute__((address_space(1))) uint16_t* w1_gptr;
-
-// K-outer image [rows][COLS] bf16: 16-B chunk ch of row r (igemm.hip kout_off, COLS >= 128);
-// the chunk XOR depends on row bits 0, 1 and 3 only
-template <int COLS>
-__device__ __forceinline__ int kout_swz_w1(int r) {
-  static_assert(COLS >= 128, "swizzle spans 16 chunks");
-  return ((r & 3) | (((r >> 3) & 1) << 2)) << 1;
-}
+// K-outer image [rows][COLS] bf16: 16-B chunk ch of row r (igemm_kernel.h kout_off, COLS >= 128);
+// the chunk XOR (kout_swz, mfma_lds.h) depends on row bits 0, 1 and 3 only
 template <int COLS>
 __device__ __forceinline__ int w1_off(int r, int ch) {
-  return r * (COLS * 2) + ((ch ^ kout_swz_w1<COLS>(r)) << 4);
+  static_assert(COLS >= 128, "swizzle spans 16 chunks");
+  return r * (COLS * 2) + ((ch ^ kout_swz<COLS>(r)) << 4);
 }
 
 struct W1Params {
@@ -133,7 +125,7 @@ __global__ __launch_bounds__(W1_NT, 1) void wgrad1x1_kernel(W1Params p) {
     else return r3;
   };
   auto ld = [&](const Chunk& ck, int step, bool ok) -> uint4 {
-    return *reinterpret_cast<const uint4*>(ok ? ck.base + (long)step * ck.stride : w1_zero16);
+    return *reinterpret_cast<const uint4*>(ok ? ck.base + (long)step * ck.stride : g_zero16);
   };
   auto load = [&](int step, Regs& r) {
     const bool ok = step < s_end;
@@ -169,8 +161,8 @@ __global__ __launch_bounds__(W1_NT, 1) void wgrad1x1_kernel(W1Params p) {
     bo_hi[j] = A_BYTES + kout(std::integral_constant<int, BN>{}, p_hi, wn * WN_COLS + 16 * j);
   }
   auto frag = [&](const unsigned char* b, int o_lo, int o_hi) -> bf16x8 {
-    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((w1_lds_bf16x4*)(b + o_lo));
-    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((w1_lds_bf16x4*)(b + o_hi));
+    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4*)(b + o_lo));
+    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4*)(b + o_hi));
     return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
   };
 
@@ -311,9 +303,9 @@ __global__ __launch_bounds__(W1_NT, 1) void wgrad1x1_pipe_kernel(W1Params p) {
   const int x_dst1 = A_BYTES + w1_off<BN>(e1 / B_CPR, e1 % B_CPR);
   const int x_dst2 = A_BYTES + w1_off<BN>(e2 / B_CPR, e2 % B_CPR);
   const int sA = 32 * p.K, sB = p.x_step;
-  w1_gptr zp = (w1_gptr)w1_zero16;
+  gptr16 zp = (gptr16)g_zero16;
   asm volatile("" : "+s"(zp));
-  const w1_gptr gdy = (w1_gptr)p.dy, gx = (w1_gptr)p.x;
+  const gptr16 gdy = (gptr16)p.dy, gx = (gptr16)p.x;
   // native vectors (a HIP uint4 read through an address-space-1 pointer becomes a memcpy
   // that keeps the ring in scratch)
   typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
@@ -361,8 +353,8 @@ __global__ __launch_bounds__(W1_NT, 1) void wgrad1x1_pipe_kernel(W1Params p) {
   for (int j = 0; j < TN; ++j) bo[j] = A_BYTES + kout(std::integral_constant<int, BN>{}, p_lo, wn * WN_COLS + 16 * j);
   auto frag = [&](const unsigned char* b, int o, auto cols_tag) __attribute__((always_inline)) -> bf16x8 {
     constexpr int COLS = decltype(cols_tag)::value;
-    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((w1_lds_bf16x4*)(b + o));
-    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((w1_lds_bf16x4*)(b + o + 4 * COLS * 2));
+    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4*)(b + o));
+    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4*)(b + o + 4 * COLS * 2));
     return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
   };
 
@@ -520,22 +512,11 @@ constexpr int W1B_NS = 4;   // LDS slots
 // guard their uses; the DMAs are ordered for the reads only by the counted vmcnt + barrier
 // of the loop. (Reads in asm instead are unsafe: hipcc may touch an asm output register --
 // a v_bfi re-packing the two halves of a fragment -- while its LDS load is still in flight.)
-__device__ __forceinline__ void w1_glds16(w1_gptr src, uint32_t lds_addr) {
+__device__ __forceinline__ void w1_glds16(gptr16 src, uint32_t lds_addr) {
   asm volatile("s_mov_b32 m0, %1\n\tglobal_load_lds_dwordx4 %0, off"
                :
                : "v"(src), "s"(__builtin_amdgcn_readfirstlane(lds_addr))
                : "memory", "m0");
-}
-template <int N>
-__device__ __forceinline__ void w1_vm_wait() {
-  static_assert(N >= 0 && N < 64, "vmcnt range");
-  __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | (7 << 4) | (15 << 8));
-  asm volatile("" ::: "memory");
-}
-__device__ __forceinline__ void w1_lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
 }
 
 template <int BN>
@@ -568,19 +549,19 @@ __global__ __launch_bounds__(W1_NT, 1) void wgrad1x1_big_kernel(W1Params p) {
   for (int i = 0; i < ND_A; ++i) {
     const int d = wv * ND_A + i;                     // wave-DMA index within the A image
     const int r = d * A_RPD + lane / A_CPR, s = lane % A_CPR;
-    a_src[i] = r * p.K + k0 + ((s ^ kout_swz_w1<W1B_BM>(r)) << 3);
+    a_src[i] = r * p.K + k0 + ((s ^ kout_swz<W1B_BM>(r)) << 3);
   }
 #pragma unroll
   for (int i = 0; i < ND_B; ++i) {
     const int d = wv * ND_B + i;
     const int r = d * B_RPD + lane / B_CPR, s = lane % B_CPR;
     const int xp = p.xst * (p.xw * (r / p.xq) + r % p.xq);
-    b_src[i] = xp * p.C + c0 + ((s ^ kout_swz_w1<BN>(r)) << 3);
+    b_src[i] = xp * p.C + c0 + ((s ^ kout_swz<BN>(r)) << 3);
   }
   const int sA = 32 * p.K, sB = p.x_step;
-  w1_gptr zp = (w1_gptr)w1_zero16;
+  gptr16 zp = (gptr16)g_zero16;
   asm volatile("" : "+s"(zp));
-  const w1_gptr gdy = (w1_gptr)p.dy, gx = (w1_gptr)p.x;
+  const gptr16 gdy = (gptr16)p.dy, gx = (gptr16)p.x;
   const uint32_t lds0 = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) unsigned char*)smem;
   auto issue = [&](int step) __attribute__((always_inline)) {
     const bool ok = step < s_end;
@@ -610,8 +591,8 @@ __global__ __launch_bounds__(W1_NT, 1) void wgrad1x1_big_kernel(W1Params p) {
   for (int j = 0; j < TN; ++j) bo[j] = A_BYTES + kout(std::integral_constant<int, BN>{}, p_lo, wn * WN_COLS + 16 * j);
   auto frag = [&](const unsigned char* b, int o, auto cols_tag) __attribute__((always_inline)) -> bf16x8 {
     constexpr int HI = 4 * decltype(cols_tag)::value * 2;
-    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((w1_lds_bf16x4*)(b + o));
-    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((w1_lds_bf16x4*)(b + o + HI));
+    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4*)(b + o));
+    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4*)(b + o + HI));
     return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
   };
 
@@ -635,8 +616,8 @@ __global__ __launch_bounds__(W1_NT, 1) void wgrad1x1_big_kernel(W1Params p) {
   };
   auto iter = [&](int k, bf16x8 (&ca)[TM], bf16x8 (&cb)[TN], bf16x8 (&na)[TM], bf16x8 (&nb)[TN])
       __attribute__((always_inline)) {
-    w1_vm_wait<2 * ND>();
-    w1_lds_barrier();
+    vm_wait<2 * ND>();
+    lds_barrier();
     read_set(k + 1, na, nb);
     issue(k + 4);
 #pragma unroll
@@ -649,14 +630,14 @@ __global__ __launch_bounds__(W1_NT, 1) void wgrad1x1_big_kernel(W1Params p) {
   issue(s_begin + 1);
   issue(s_begin + 2);
   issue(s_begin + 3);
-  w1_vm_wait<3 * ND>();
-  w1_lds_barrier();
+  vm_wait<3 * ND>();
+  lds_barrier();
   read_set(s_begin, fa0, fb0);
   for (int k = s_begin; k < s_end; k += 2) {
     iter(k, fa0, fb0, fa1, fb1);
     if (k + 1 < s_end) iter(k + 1, fa1, fb1, fa0, fb0);
   }
-  w1_vm_wait<0>();   // the tail DMAs (zero page) land before the block's LDS is released
+  vm_wait<0>();   // the tail DMAs (zero page) land before the block's LDS is released
 
   float* out = p.part + (size_t)split * p.K * p.C;
 #pragma unroll

@@ -2,7 +2,7 @@
 //
 //   dW[k][r][s][c] = Σ_{n,h,w} dy[n][h][w][k] · x[n][h+r−1][w+s−1][c]
 //
-// The generic implicit-GEMM wgrad (igemm.hip, MODE_WGRAD) treats the 9 taps as 9 separate
+// The generic implicit-GEMM wgrad (igemm_wgrad.hip) treats the 9 taps as 9 separate
 // column tiles, so every tap tile re-reads the dy tile and its own shifted copy of x. Here
 // one 512-thread block owns 64 output channels × 64 input channels × ALL 9 taps (576 GEMM
 // columns) and walks its K-split 32 pixels at a time: per step it stages the 32×64 dy tile
@@ -24,11 +24,12 @@
 // W=16/32 read within one row). Fragments follow igemm.hip's convention: the MFMA is issued
 // as D = Bᵀ·Aᵀ, so each lane holds 4 consecutive output columns of one output row. Output:
 // an fp32 partial slab per K-split, reduced deterministically by the split-K reduction of
-// igemm.hip (no atomics).
+// splitk.hip (no atomics).
 #include <type_traits>
 
 #include "common.h"
 #include "launchers.h"
+#include "mfma_lds.h"
 
 using namespace sdx;
 
@@ -47,10 +48,6 @@ constexpr int W3_ROWB = 128;    // LDS row: 64 bf16
 constexpr int W3_DY_BYTES = 32 * W3_ROWB;
 constexpr int W3_PF = 4;        // steps of loads in flight (register ring of 4 named slots)
 
-typedef __attribute__((address_space(3))) bf16x4 w3_lds_bf16x4;
-
-__device__ __attribute__((aligned(16))) uint16_t w3_zero16[8];
-typedef const __attribute__((address_space(1))) uint16_t* w3_gptr;
 typedef unsigned int w3_u32x4 __attribute__((ext_vector_type(4)));   // (a HIP uint4 cannot be read
 typedef const __attribute__((address_space(1))) w3_u32x4* w3_g16;     //  through an AS-1 pointer)
 
@@ -115,19 +112,19 @@ __global__ __launch_bounds__(W3_NT, 1) void wgrad3x3_kernel(W3Params p) {
   // zero page pinned in an SGPR pair: otherwise every select re-materialises its address
   // (s_getpc + a GOT load + lgkmcnt(0), which also drains this wave's LDS traffic) and the
   // divergent selects become exec-masked branches
-  w3_gptr zp = (w3_gptr)w3_zero16;
+  gptr16 zp = (gptr16)g_zero16;
   asm volatile("" : "+s"(zp));
   struct XChunk {
-    w3_gptr base;   // x element of step 0 (may lie outside x: used only when valid)
+    gptr16 base;   // x element of step 0 (may lie outside x: used only when valid)
     int i, r;       // window image row within the step, tap row
   };
   auto x_chunk = [&](int e) -> XChunk {
     const int ch = e & 7, rest = e >> 3;
     const int w = rest % W, ri = rest / W;
     const int r = ri / RPS, i = ri % RPS;
-    return {(w3_gptr)p.x + ((long)(i + r - 1) * W + w) * p.C + c0 + ch * 8, i, r};
+    return {(gptr16)p.x + ((long)(i + r - 1) * W + w) * p.C + c0 + ch * 8, i, r};
   };
-  auto x_src = [&](const XChunk& xc, int step) -> w3_gptr {
+  auto x_src = [&](const XChunk& xc, int step) -> gptr16 {
     const int hs = ((step * RPS + xc.i) & (W - 1)) + xc.r - 1;   // H == W
     const bool ok = step < s_end && (unsigned)hs < (unsigned)W;
     return ok ? xc.base + (long)step * 32 * p.C : zp;
@@ -141,7 +138,7 @@ __global__ __launch_bounds__(W3_NT, 1) void wgrad3x3_kernel(W3Params p) {
   const int dst0 = first_dy ? w3_off(tid >> 3, tid & 7) : x_dst(e0);
   const int dst1 = x_dst(e1);
   const XChunk xc0 = x_chunk(first_dy ? 0 : e0), xc1 = x_chunk(e1);
-  const w3_gptr dy_base = (w3_gptr)p.dy + (long)(tid >> 3) * p.K + k0 + (tid & 7) * 8;
+  const gptr16 dy_base = (gptr16)p.dy + (long)(tid >> 3) * p.K + k0 + (tid & 7) * 8;
   // register ring of 4 prefetched steps: slot u holds the step ≡ s_begin + u (mod 4). Named
   // registers selected at compile time (an array indexed inside the lambdas goes to scratch)
   w3_u32x4 ra0, rb0, ra1, rb1, ra2, rb2, ra3, rb3;
@@ -158,7 +155,7 @@ __global__ __launch_bounds__(W3_NT, 1) void wgrad3x3_kernel(W3Params p) {
     else return rb3;
   };
   auto load = [&](int step, w3_u32x4& a, w3_u32x4& b) {
-    const w3_gptr s0 = first_dy ? (step < s_end ? dy_base + (long)step * 32 * p.K : zp) : x_src(xc0, step);
+    const gptr16 s0 = first_dy ? (step < s_end ? dy_base + (long)step * 32 * p.K : zp) : x_src(xc0, step);
     a = *(w3_g16)s0;
     b = *(w3_g16)x_src(xc1, step);
   };
@@ -193,8 +190,8 @@ __global__ __launch_bounds__(W3_NT, 1) void wgrad3x3_kernel(W3Params p) {
     bo_hi[j] = W3_DY_BYTES + lane_off(xb_hi + off, n & 63);
   }
   auto frag = [&](const unsigned char* base, int o_lo, int o_hi) -> bf16x8 {
-    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((w3_lds_bf16x4*)(base + o_lo));
-    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((w3_lds_bf16x4*)(base + o_hi));
+    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4*)(base + o_lo));
+    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4*)(base + o_hi));
     return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
   };
 
@@ -337,10 +334,10 @@ __global__ __launch_bounds__(W3_NT, 1) void wgrad3x3_s2_kernel(W3Params p) {
   // chunk f%8), else x chunk e = f − 256: channel chunk e%8 of input column e/8 % 2Q of
   // window row ri = e/(16Q) = (r, i). Output row Rg = step·RPS + i (global over images, H =
   // 2P) reads input row 2Rg + r − 1: x element base + step·(2·RPS·W·C)
-  w3_gptr zp = (w3_gptr)w3_zero16;   // pinned in SGPRs (see wgrad3x3_kernel)
+  gptr16 zp = (gptr16)g_zero16;   // pinned in SGPRs (see wgrad3x3_kernel)
   asm volatile("" : "+s"(zp));
   struct XChunk {
-    w3_gptr base;   // element of step 0 (used only when valid)
+    gptr16 base;   // element of step 0 (used only when valid)
     int i, r, dst;
     bool cok;       // input column inside the image (PAD)
   };
@@ -349,11 +346,11 @@ __global__ __launch_bounds__(W3_NT, 1) void wgrad3x3_s2_kernel(W3Params p) {
     const int col = rest % W, ri = rest / W;
     const int r = ri / RPS, i = ri % RPS;
     const int lrow = ri * G::PT + ((col & 1) ? (col + 1) >> 1 : Q + 1 + (col >> 1));
-    return {(w3_gptr)p.x + ((long)(2 * i + r - 1) * Wr + col) * p.C + c0 + ch * 8, i, r, W3_DY_BYTES + w3_off(lrow, ch),
+    return {(gptr16)p.x + ((long)(2 * i + r - 1) * Wr + col) * p.C + c0 + ch * 8, i, r, W3_DY_BYTES + w3_off(lrow, ch),
             col < Wr};
   };
   const long x_step = 2L * RPS * Wr * p.C;
-  auto x_src = [&](const XChunk& xc, int step) -> w3_gptr {
+  auto x_src = [&](const XChunk& xc, int step) -> gptr16 {
     const int ho = PAD ? (step * RPS + xc.i) % pq : (step * RPS + xc.i) & (Q - 1);
     const int hi = 2 * ho + xc.r - 1;   // input row within the image
     const bool ok = step < s_end && (unsigned)hi < (unsigned)Wr && (!PAD || xc.cok);
@@ -367,8 +364,8 @@ __global__ __launch_bounds__(W3_NT, 1) void wgrad3x3_s2_kernel(W3Params p) {
   const int dslot = tid >> 3;
   const bool dy_ok = !PAD || dslot % Q < pq;
   const long dy_step = PAD ? (long)RPS * pq * p.K : 32L * p.K;
-  const w3_gptr dy_base =
-      (w3_gptr)p.dy + (long)(PAD ? (dslot / Q) * pq + dslot % Q : dslot) * p.K + k0 + (tid & 7) * 8;
+  const gptr16 dy_base =
+      (gptr16)p.dy + (long)(PAD ? (dslot / Q) * pq + dslot % Q : dslot) * p.K + k0 + (tid & 7) * 8;
   // 2-step register ring of named vectors (a struct of uint4 read through the lambdas ends up
   // in scratch)
   w3_u32x4 ra0, rb0, rc0, rd0, ra1, rb1, rc1, rd1;
@@ -412,8 +409,8 @@ __global__ __launch_bounds__(W3_NT, 1) void wgrad3x3_s2_kernel(W3Params p) {
     bo_hi[j] = W3_DY_BYTES + lane_off(xrow(p_hi, r, s_), n & 63);
   }
   auto frag = [&](const unsigned char* base, int o_lo, int o_hi) -> bf16x8 {
-    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((w3_lds_bf16x4*)(base + o_lo));
-    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((w3_lds_bf16x4*)(base + o_hi));
+    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4*)(base + o_lo));
+    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4*)(base + o_hi));
     return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
   };
 
@@ -525,9 +522,9 @@ __global__ __launch_bounds__(W3_NT, 1) void wgrad3x3_pad_kernel(W3Params p) {
   const int s_begin = split * p.steps_per_split;
   const int s_end = min(p.steps_total, s_begin + p.steps_per_split);
 
-  w3_gptr zp = (w3_gptr)w3_zero16;   // pinned in SGPRs (see wgrad3x3_kernel)
+  gptr16 zp = (gptr16)g_zero16;   // pinned in SGPRs (see wgrad3x3_kernel)
   asm volatile("" : "+s"(zp));
-  const w3_gptr gdy = (w3_gptr)p.dy, gx = (w3_gptr)p.x;
+  const gptr16 gdy = (gptr16)p.dy, gx = (gptr16)p.x;
   // loader: chunk f = tid + 512u (u < 3): f < 256 a dy chunk (slot f/8, channel chunk f%8),
   // else x chunk e = f − 256 < XCH: channel chunk e%8 of window column e/8 % (SW+2) of window
   // row e/(8(SW+2)) = (r, i)
@@ -543,7 +540,7 @@ __global__ __launch_bounds__(W3_NT, 1) void wgrad3x3_pad_kernel(W3Params p) {
     return {ri % RPS, cw - 1, ri / RPS, ch, true, e < G::XCH, W3_DY_BYTES + w3_off(ri * G::P + cw, ch)};
   };
   const Src sa = chunk(tid), sb = chunk(tid + 512), sc = chunk(tid + 1024);
-  auto src = [&](const Src& c, int step) -> w3_gptr {
+  auto src = [&](const Src& c, int step) -> gptr16 {
     const int seg = step * RPS + c.i;
     const int rg = seg / SPR, w = (seg % SPR) * SW + c.col;   // image row (global), column
     const int hs = rg % H + c.r - 1;                           // source row within the image
@@ -588,8 +585,8 @@ __global__ __launch_bounds__(W3_NT, 1) void wgrad3x3_pad_kernel(W3Params p) {
     bo_hi[j] = W3_DY_BYTES + lane_off(xb_hi + off, n & 63);
   }
   auto frag = [&](const unsigned char* base, int o_lo, int o_hi) -> bf16x8 {
-    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((w3_lds_bf16x4*)(base + o_lo));
-    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((w3_lds_bf16x4*)(base + o_hi));
+    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4*)(base + o_lo));
+    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4*)(base + o_hi));
     return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
   };
   f32x4 acc[2][9];

@@ -1,4 +1,9 @@
 """Implicit-GEMM MFMA convolution kernels vs fp32 torch convolution (GPU)."""
+import json
+import os
+import subprocess
+import sys
+
 import pytest
 import torch
 import torch.nn.functional as F
@@ -508,3 +513,35 @@ def test_single_stage_loop_matches_two_stage(gpu, mode, shape):
     if mode == "fwd":
         ref = F.conv2d(x.float(), w.float())
         assert _rel(outs[1][0].permute(0, 3, 1, 2), ref) < 1e-2
+
+
+TRACE_SCRIPT = r"""
+import json, torch
+from simclr_pytorch_distributed_amd.ops import _ext
+m = _ext.require()
+x = torch.randn(1, 8, 8, 64, device="cuda").bfloat16()
+w = (torch.randn(64, 1, 1, 64, device="cuda") * 0.1).bfloat16()
+m.conv_fwd(x, w, 1, 0, True, 3)
+fwd = m.igemm_trace()[0].tolist()
+m.conv_dgrad(x, w.permute(3, 1, 2, 0).contiguous(), 8, 8, 1, 0, 3)
+dgrad = m.igemm_trace()[0].tolist()
+print("TRACE " + json.dumps([fwd, dgrad]))
+"""
+
+
+def test_igemm_trace_follows_the_last_traced_family(gpu):
+    """The forward and data-gradient kernels live in different translation units, each with
+    its own trace buffer; igemm_trace() must read the buffer of the unit that launched last
+    (a copy from another unit's buffer would return zeros or a stale timeline). One 1x1
+    conv at N=1, 8x8, 64 -> 64, cfg 3, forward then stride-1 dgrad, in a child process
+    (SDX_IGEMM_TRACE is read once, at the first launch): wave 0's start stamp (slot 0) and
+    end stamp (slot -2) are non-zero and ordered after each, and the dgrad's differ from
+    the forward's."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, SDX_IGEMM_TRACE="1", PYTHONPATH=root)
+    r = subprocess.run([sys.executable, "-c", TRACE_SCRIPT], env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
+    fwd, dgrad = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("TRACE ")][-1][6:])
+    for t in (fwd, dgrad):
+        assert 0 < t[0] < t[-2], (t[0], t[-2])
+    assert dgrad[0] != fwd[0] and dgrad[-2] != fwd[-2], (fwd[0], fwd[-2], dgrad[0], dgrad[-2])

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Main-loop timeline of one conv launch (SDX_IGEMM_TRACE=1 is set here): block 0, waves 0
 (group 0) and 4 (group 1) of the ping-pong loop; per K-tile the cycles of the load segment
-(fragment reads + DMA issue + wait), the barrier wait, and the MFMA issue.
+(fragment reads + DMA issue + wait), the barrier wait, and the MFMA issue. The stamps are
+written by igemm_kernel.h (slot layout at kTraceSlots); m.igemm_trace() returns those of the
+last traced launch, whichever unit (igemm_fwd / dgrad / wgrad / tap .hip) ran it.
 
 python tools/igemm_trace.py --mode fwd --shape 512,8,8,256,256,3,1,1 --cfg 6
 """
