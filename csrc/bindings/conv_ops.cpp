@@ -497,6 +497,14 @@ void register_conv(pybind11::module& m) {
         pybind11::arg("in_shift") = pybind11::none());
   m.def("splitk_merge_set", [](bool on) { return (int64_t)splitk_merge_flag().exchange(on ? 1 : 0); },
         "merge a residual block's side-stream split-K reductions into one launch (returns the previous setting)");
+  // test hooks of the deferred multi-tensor split-K reduction (splitk.hip), which block_bwd
+  // alone reaches otherwise: host-only, on the current stream (a non-default one: the null
+  // stream never defers). Slabs queued meanwhile live in side_stash until side_stash_release.
+  m.def("splitk_defer_begin", [] { splitk_defer_begin(cur_stream()); },
+        "queue the current stream's split-K reductions until splitk_defer_flush (tests)");
+  m.def("splitk_defer_flush", [] { check_hip(splitk_flush(), "splitk_defer_flush"); },
+        "issue the queued split-K reductions as one multi-tensor launch and stop deferring (tests)");
+  m.def("splitk_defer_cancel", [] { splitk_defer_cancel(); }, "drop the queue and stop deferring (tests)");
   m.def("conv_dgrad_bnstat",
         [](torch::Tensor dy, torch::Tensor wt, int64_t H, int64_t W, int64_t stride, int64_t pad, int64_t cfg, OptT out,
            OptT addend, OptT addend_mask, torch::Tensor ya, torch::Tensor ma, OptT yb, OptT mb, OptT mask_bits,

@@ -1,7 +1,7 @@
 """Conv dispatch plan (host-only, CPU): which tile config auto dispatch gives every stride-1
 3x3 conv of the two benchmark configs, and how many statistics-slab rows its launch writes.
 
-Covers the padded-row tap-reuse tiles (igemm.hip tap_geom t_rw): at 56x56 (224x224 config,
+Covers the padded-row tap-reuse tiles (conv_plan.h tap_geom t_rw): at 56x56 (224x224 config,
 stage 1) a 256-row tile holds 4 image rows of 64 virtual pixels (56 real), so the slab has
 N*H*64/256 rows, not ceil(N*H*W/256). The plan is computed by the extension's host code
 only (`conv_plan`), no kernel runs.

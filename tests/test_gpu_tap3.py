@@ -20,7 +20,7 @@ HALO_KB = {256: 50, 128: 36}
 
 
 def tap_geom(cfg, H, W, cdim):
-    """Python mirror of igemm.hip tap_geom: None if the tap cfg rejects the geometry, else the
+    """Python mirror of tap_geom (csrc/include/conv_plan.h): None if the tap cfg rejects the geometry, else the
     virtual row width of a padded-row tile (0: unpadded)."""
     bm = TAP_BM[cfg]
     if cdim % 64:
