@@ -151,6 +151,8 @@ void register_supcon(pybind11::module& m) {
   m.def("rownorm_fwd", &rownorm_fwd, "row L2 normalisation (F.normalize dim=1) -> (y, norms)");
   m.def("rownorm_bwd", &rownorm_bwd, "gradient of row L2 normalisation");
   m.def("norm_stats", &norm_stats, "SEC/L2-reg feature-norm statistics + record_norm_mean EMA (one launch)");
+  m.def("supcon_num_splits", [](int n_own, int n_other) { return supcon_num_splits(n_own, n_other); },
+        "split count of the tile kernel for n_own own rows against n_other other rows (read-only)");
   m.def("supcon_fwd", &supcon_fwd, "fused SupCon/NT-Xent forward (row form)");
   m.def("supcon_bwd", &supcon_bwd, "fused SupCon/NT-Xent backward (row form)");
   m.def("supcon_bwd_sum", &supcon_bwd_sum, "SupCon backward when anchors are the contrasts: dA + dC in one reduce");

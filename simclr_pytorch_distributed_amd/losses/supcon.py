@@ -12,8 +12,9 @@ materialised. That row form is what the fused gfx950 kernel (``ops/contrastive.p
 implements, and what lets each rank own only its anchors while contrasting against
 the globally gathered matrix.
 
-Deviation: anchors with no positive (possible only for SupCon with a unique label in
-``contrast_mode='one'``) contribute 0 instead of the reference's NaN.
+Deviation: anchors with no positive contribute 0 instead of the reference's NaN. With two or
+more views every anchor has its other views, so this is reachable only through the row form
+with arbitrary keys, or with ``n_views`` = 1 (SimCLR keys, or a SupCon label that occurs once).
 """
 from __future__ import annotations
 
