@@ -1,6 +1,7 @@
 // Linear-probe classifier (linear_ce.hip): fused logits + cross-entropy + top-k hits, and
 // the gradient + SGD update, for the native linear evaluation (ops/linear_probe.py;
-// reference main_linear.py:166-244); ce_head_fwd / ce_head_bwd: the same classifier as a
+// reference main_linear.py:166-244); linear_ce_sweep_step: G such classifiers with their own
+// lr / wd on one feature batch (linear_ce_sweep.hip); ce_head_fwd / ce_head_bwd: the same classifier as a
 // trainable node of the supervised model (ops/ce_head.py; reference main_ce.py), whose
 // parameter gradients accumulate into the gradient sinks.
 #include "conv_internal.h"
@@ -61,6 +62,67 @@ std::vector<torch::Tensor> linear_ce_step(torch::Tensor x, torch::Tensor W, torc
                                  (float)lr, (float)momentum, (float)wd, first ? 1 : 0, rowstat.data_ptr<float>(),
                                  stats.data_ptr<float>(), cur_stream()),
             "linear_ce_sgd");
+  return {logits, stats};
+}
+
+// One batch of a hyper-parameter sweep (linear_ce_sweep.hip): G classifiers W [G][C][K], b [G][C]
+// on the same features x [B][K], head g with lrs[g] / wds[g]; momentum and `first` are shared.
+// train: bufW [G][C][K], bufb [G][C]; eval: no buffers. Views of larger tensors are allowed when
+// contiguous and 16-byte aligned. Everything is checked before anything is allocated or launched.
+// Returns [logits [G][B][C], stats [G][3]]; head g is bit-identical to linear_ce_step alone.
+std::vector<torch::Tensor> linear_ce_sweep_step(torch::Tensor x, torch::Tensor W, torch::Tensor b,
+                                                torch::Tensor labels, OptT bufW, OptT bufb, std::vector<double> lrs,
+                                                double momentum, std::vector<double> wds, bool first, bool train) {
+  TORCH_CHECK(x.dim() == 2 && W.dim() == 3, "x [B][K], W [G][C][K]");
+  const int64_t B = x.size(0), K = x.size(1), G = W.size(0), C = W.size(1);
+  TORCH_CHECK(G >= 1 && G <= kLinearSweepMaxHeads, "linear_ce_sweep: 1 <= G <= ", kLinearSweepMaxHeads, ", got ", G);
+  TORCH_CHECK((int64_t)lrs.size() == G && (int64_t)wds.size() == G, "linear_ce_sweep: ", G, " heads need ", G,
+              " learning rates and weight decays, got ", lrs.size(), " and ", wds.size());
+  check_f32(x, {B, K}, "x");
+  check_f32(W, {G, C, K}, "W");
+  check_f32(b, {G, C}, "b");
+  TORCH_CHECK(labels.is_cuda() && labels.scalar_type() == at::kLong && labels.numel() == B && labels.is_contiguous(),
+              "labels: int64 [B]");
+  TORCH_CHECK(B >= 1 && linear_ce_sweep_supported((int)G, (int)K, (int)C),
+              "linear_ce_sweep: K = 64·2^j <= 2048, 1 <= C <= 1024, B >= 1");
+  TORCH_CHECK(G * B * C < (1LL << 31) && B * K < (1LL << 31) && G * C * K < (1LL << 31), "linear_ce_sweep: sizes");
+  auto aligned = [](const torch::Tensor& t) { return reinterpret_cast<uintptr_t>(t.data_ptr<float>()) % 16 == 0; };
+  TORCH_CHECK(aligned(x) && aligned(W), "linear_ce_sweep: x and W must be 16-byte aligned");
+  const int dev = x.get_device();
+  TORCH_CHECK(W.get_device() == dev && b.get_device() == dev && labels.get_device() == dev,
+              "linear_ce_sweep: one device");
+  if (train) {
+    TORCH_CHECK(bufW.has_value() && bufb.has_value(), "momentum buffers required for a training step");
+    check_f32(*bufW, {G, C, K}, "bufW");
+    check_f32(*bufb, {G, C}, "bufb");
+    TORCH_CHECK(bufW->get_device() == dev && bufb->get_device() == dev, "linear_ce_sweep: one device");
+    TORCH_CHECK(aligned(*bufW), "linear_ce_sweep: bufW must be 16-byte aligned");
+  }
+  c10::DeviceGuard dg(x.device());
+  auto fo = x.options();
+  auto logits = torch::empty({G, B, C}, fo);
+  auto rowstat = torch::empty({G, B, 3}, fo);
+  auto stats = torch::empty({G, 3}, fo);
+  torch::Tensor dz;
+  if (train) dz = torch::empty({G, B, C}, fo);
+  float lr[kLinearSweepMaxHeads], wd[kLinearSweepMaxHeads];
+  for (int64_t g = 0; g < G; ++g) {
+    lr[g] = (float)lrs[g];
+    wd[g] = (float)wds[g];
+  }
+  check_hip(launch_linear_ce_sweep_fwd(x.data_ptr<float>(), W.data_ptr<float>(), b.data_ptr<float>(),
+                                       labels.data_ptr<int64_t>(), (int)G, (int)B, (int)K, (int)C, (float)(1.0 / B),
+                                       logits.data_ptr<float>(), train ? dz.data_ptr<float>() : nullptr,
+                                       rowstat.data_ptr<float>(), cur_stream()),
+            "linear_ce_sweep_fwd");
+  check_hip(launch_linear_ce_sweep_sgd(x.data_ptr<float>(), train ? dz.data_ptr<float>() : nullptr, (int)G, (int)B,
+                                       (int)K, (int)C, train ? W.data_ptr<float>() : nullptr,
+                                       train ? b.data_ptr<float>() : nullptr,
+                                       train ? bufW->data_ptr<float>() : nullptr,
+                                       train ? bufb->data_ptr<float>() : nullptr, lr, wd, (float)momentum,
+                                       first ? 1 : 0, rowstat.data_ptr<float>(), stats.data_ptr<float>(),
+                                       cur_stream()),
+            "linear_ce_sweep_sgd");
   return {logits, stats};
 }
 
@@ -144,6 +206,12 @@ void register_probe(pybind11::module& m) {
         "linear classifier + mean cross-entropy + top-1/5 hits (+ gradient and SGD update when train)",
         pybind11::arg("x"), pybind11::arg("W"), pybind11::arg("b"), pybind11::arg("labels"), pybind11::arg("bufW"),
         pybind11::arg("bufb"), pybind11::arg("lr"), pybind11::arg("momentum"), pybind11::arg("wd"),
+        pybind11::arg("first"), pybind11::arg("train"));
+  m.def("linear_ce_sweep_step", &linear_ce_sweep_step,
+        "G linear classifiers with per-head lr / wd on one feature batch: logits [G][B][C], stats [G][3] "
+        "(+ gradients and SGD updates when train); head g is bit-identical to linear_ce_step",
+        pybind11::arg("x"), pybind11::arg("W"), pybind11::arg("b"), pybind11::arg("labels"), pybind11::arg("bufW"),
+        pybind11::arg("bufb"), pybind11::arg("lrs"), pybind11::arg("momentum"), pybind11::arg("wds"),
         pybind11::arg("first"), pybind11::arg("train"));
 }
 

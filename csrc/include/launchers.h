@@ -35,6 +35,21 @@ hipError_t launch_ce_head_bwd(const float* x, const float* dz, const float* W, i
                               float* dX, float* dW, float* db, const float* rowstat, float* stats, float* loss,
                               hipStream_t s);
 
+// ---- linear-probe sweep: G classifiers on one feature batch (linear_ce_sweep.hip) ----
+// W [G][C][K], bias [G][C], buffers alike, logits / dz [G][B][C], rowstat [G][B][3], stats [G][3].
+// Supported: 1 <= G <= 16, K = 64·2^j <= 2048, 1 <= C <= 1024, B >= 1, G·B·C, B·K and G·C·K
+// below 2^31, x / W / bufW 16-byte aligned; everything else is hipErrorInvalidValue before any
+// launch. Head g is bit-identical to the single-head pair above with that head's lr and wd.
+constexpr int kLinearSweepMaxHeads = 16;
+bool linear_ce_sweep_supported(int G, int K, int C);
+hipError_t launch_linear_ce_sweep_fwd(const float* x, const float* W, const float* bias, const int64_t* labels, int G,
+                                      int B, int K, int C, float gscale, float* logits, float* dz, float* rowstat,
+                                      hipStream_t s);
+// lrs / wds: G host values (passed to the kernel by value); W == nullptr: statistics only
+hipError_t launch_linear_ce_sweep_sgd(const float* x, const float* dz, int G, int B, int K, int C, float* W,
+                                      float* bias, float* bufW, float* bufb, const float* lrs, const float* wds,
+                                      float mom, int first, const float* rowstat, float* stats, hipStream_t s);
+
 // ---- fused SupCon / NT-Xent loss (supcon.hip) ---------------------------------
 int supcon_num_splits(int n_own, int n_other);
 hipError_t launch_supcon_fwd(const float* A, const float* C, const int* a_self, const int* a_key,

@@ -16,7 +16,8 @@ Additions (new flags only; no reference flag changes meaning):
 ``--knn_freq`` / ``--knn`` with ``--knn_k`` / ``--knn_t`` (weighted k-NN monitor, engine/knn.py),
 ``--blur_p`` / ``--blur_kernel`` / ``--blur_sigma`` (Gaussian-blur augmentation, data/augment.py),
 ``--val_folder`` / ``--resize`` (ImageFolder evaluation: Resize + CenterCrop on the GPU; the linear
-probe also takes ``--dataset path`` with ``--size`` / ``--mean`` / ``--std``).
+probe also takes ``--dataset path`` with ``--size`` / ``--mean`` / ``--std``),
+``--sweep_lr`` / ``--sweep_wd`` (linear probe: one classifier per (lr, wd) pair on one encoder pass).
 Fixes: ``--num_workers`` is honoured (Q6): it sizes the image-decode thread pool of
 ``dataset=path`` and the CPU augmentation threads of ``--gpu_aug 0`` (the default pipeline
 is the GPU kernel, which needs no workers); ``dataset=path`` parses ``--mean/--std``
@@ -315,13 +316,57 @@ def linear_parser() -> argparse.ArgumentParser:
     g.add_argument("--mean", type=str, help="mean of dataset in path in form of str tuple")
     g.add_argument("--std", type=str, help="std of dataset in path in form of str tuple")
     _add_eval_flags(g)
+    g.add_argument("--sweep_lr", type=float, nargs="+", default=None, metavar="LR",
+                   help="train one classifier per learning rate on the same encoder pass (with --sweep_wd: "
+                        "one per (lr, wd) pair, at most 16) and report the best")
+    g.add_argument("--sweep_wd", type=float, nargs="+", default=None, metavar="WD",
+                   help="weight decays of the sweep (absent: --weight_decay)")
     _add_common_new_flags(p)
     return p
 
 
+SWEEP_MAX_HEADS = 16
+
+
+def _sweep_heads(parser, opt):
+    """``opt.sweep``: None, or the (lr, wd) of every head of --sweep_lr x --sweep_wd, lr-major; an
+    absent list stands for the single --learning_rate / --weight_decay."""
+    lrs, wds = opt.sweep_lr, opt.sweep_wd
+    del opt.sweep_lr, opt.sweep_wd
+    opt.sweep = None
+    if lrs is None and wds is None:
+        return
+    lrs = [opt.learning_rate] if lrs is None else lrs
+    wds = [opt.weight_decay] if wds is None else wds
+    if any(not lr > 0 for lr in lrs):
+        parser.error("--sweep_lr: every learning rate must be positive")
+    if any(not wd >= 0 for wd in wds):
+        parser.error("--sweep_wd: a weight decay cannot be negative")
+    if len(lrs) * len(wds) > SWEEP_MAX_HEADS:
+        parser.error(f"--sweep_lr x --sweep_wd gives {len(lrs) * len(wds)} heads; at most {SWEEP_MAX_HEADS}")
+    opt.sweep = [(float(lr), float(wd)) for lr in lrs for wd in wds]
+
+
+def sweep_head_opts(opt):
+    """One copy of ``opt`` per sweep head with that head's ``learning_rate``, ``weight_decay`` and,
+    with --warm, ``warmup_to``: the schedules (optim/schedules.py) read these."""
+    import copy
+    heads = []
+    for lr, wd in opt.sweep:
+        o = copy.copy(opt)
+        o.learning_rate, o.weight_decay = lr, wd
+        name = o.model_name
+        _warm_fields(o)
+        o.model_name = name
+        heads.append(o)
+    return heads
+
+
 def parse_linear(argv: Optional[Sequence[str]] = None, make_dirs: bool = True,
                  now: Optional[datetime.datetime] = None):
-    opt = linear_parser().parse_args(argv)
+    parser = linear_parser()
+    opt = parser.parse_args(argv)
+    _sweep_heads(parser, opt)
     if opt.knn_k < 1 or not opt.knn_t > 0:
         raise ValueError("--knn_k >= 1 and --knn_t > 0 are required")
     if opt.size < 1:
@@ -340,6 +385,8 @@ def parse_linear(argv: Optional[Sequence[str]] = None, make_dirs: bool = True,
     if opt.cosine:
         opt.model_name = f"{opt.model_name}_cosine"
     _warm_fields(opt)
+    if opt.sweep is not None:
+        opt.model_name = f"{opt.model_name}_sweep{len(opt.sweep)}"
     # path: the class count comes from the dataset at engine start
     opt.n_cls = N_CLASSES.get(opt.dataset, 0)
     now = now or datetime.datetime.now()

@@ -12,9 +12,15 @@ Native backend (ops/linear_probe.py): the frozen encoder runs 
 eval-mode BatchNorm folded into its conv (one implicit-GEMM launch per conv + BN + ReLU, no
 BN kernels), and the classifier's logits, cross-entropy, top-1/5 hits, gradient and SGD
 update are two fused launches per batch; the meters stay on the device.
+
+Sweep (``--sweep_lr`` / ``--sweep_wd``): G classifiers, one per (lr, wd) pair, are trained on
+the same encoder pass, each on the reference schedule for its own base lr; on the native path
+all of them are the same two launches (ops/linear_probe.py ``NativeLinearSweep``), elsewhere a
+loop over G torch classifiers. Every head computes what a single run with its settings computes.
 """
 from __future__ import annotations
 
+import copy
 import logging
 import sys
 import time
@@ -22,13 +28,14 @@ from typing import Optional
 
 import torch
 
+from ..config import sweep_head_opts
 from ..data.augment import AugConfig
 from ..data.sampler import DistributedIndexSampler
 from ..data.store import probe_stores
 from ..models.executor import ModelRunner
 from ..models.resnet import LinearClassifier, SupConResNet
 from ..ops import linear_probe
-from ..optim.schedules import adjust_learning_rate, warmup_learning_rate
+from ..optim.schedules import adjust_learning_rate, lr_at_epoch, set_lr, warmup_learning_rate, warmup_lr
 from ..parallel import comm
 from ..utils.logging import setup_logging
 from ..utils.meters import AverageMeter, accuracy
@@ -76,9 +83,171 @@ class LinearEngine:
         self.criterion = torch.nn.CrossEntropyLoss()
         self.optimizer = torch.optim.SGD(self.classifier.parameters(), lr=opt.learning_rate, momentum=opt.momentum,
                                          weight_decay=opt.weight_decay)
+        # --sweep_lr / --sweep_wd: G heads, every one a copy of the classifier above, trained on
+        # the same features with their own lr schedule and weight decay
+        self.sweep = getattr(opt, "sweep", None)
+        self.sweep_results = None
+        self.native_sweep = None
+        if self.sweep:
+            self.head_opts = sweep_head_opts(opt)
+            self.head_lrs = [lr for lr, _ in self.sweep]
+            wds = [wd for _, wd in self.sweep]
+            if self.backend == "native" and linear_probe.sweep_supported(self.classifier, len(self.sweep)):
+                self.native_sweep = linear_probe.NativeLinearSweep(self.classifier, wds, opt.momentum)
+            else:
+                self.classifiers = [copy.deepcopy(self.classifier) for _ in self.sweep]
+                self.optimizers = [torch.optim.SGD(c.parameters(), lr=lr, momentum=opt.momentum, weight_decay=wd)
+                                   for c, (lr, wd) in zip(self.classifiers, self.sweep)]
         from ..utils.tb import Logger
         self.logger = Logger(opt.tb_folder, flush_secs=2)
         self.prof = PhaseTimer(getattr(opt, "profile", False), dev)
+
+    def head_state(self, g: int):
+        """``LinearClassifier`` state dict of sweep head ``g``."""
+        if self.native_sweep is not None:
+            return self.native_sweep.head_state(g)
+        return {k: v.detach().clone() for k, v in self.classifiers[g].state_dict().items()}
+
+    def _classify_sweep(self, feats, labels, train: bool):
+        """(logits [G, B, C], loss [G], acc1 [G], acc5 [G]) of a batch — device tensors; every
+        value is computed as ``_classify`` computes a single classifier's."""
+        bsz = labels.shape[0]
+        if self.native_sweep is not None:
+            if train:
+                out, st = self.native_sweep.train_batch(feats, labels, self.head_lrs)
+            else:
+                out, st = self.native_sweep.eval_batch(feats, labels)
+            return out, st[:, 0] / bsz, st[:, 1] * (100.0 / bsz), st[:, 2] * (100.0 / bsz)
+        outs, losses, a1s, a5s = [], [], [], []
+        for clf, optim in zip(self.classifiers, self.optimizers):
+            output = clf(feats.detach())
+            loss = self.criterion(output, labels)
+            acc1, acc5 = accuracy(output, labels, topk=(1, 5))
+            if train:
+                optim.zero_grad()
+                loss.backward()
+                optim.step()
+            outs.append(output.detach())
+            losses.append(loss.detach())
+            a1s.append(acc1[0])
+            a5s.append(acc5[0])
+        return torch.stack(outs), torch.stack(losses), torch.stack(a1s), torch.stack(a5s)
+
+    def _set_head_lrs(self, lrs):
+        """``lrs[g]`` where it is not None becomes head g's learning rate."""
+        for g, lr in enumerate(lrs):
+            if lr is None:
+                continue
+            self.head_lrs[g] = lr
+            if self.native_sweep is None:
+                set_lr(self.optimizers[g], lr)
+
+    def _train_epoch_sweep(self, epoch):
+        """``train_epoch`` for G heads: per-head (loss, acc1, acc5) lists; the window line reports head 0."""
+        opt = self.opt
+        G = len(self.sweep)
+        self.sampler.set_epoch(epoch)
+        iters = len(self.sampler)
+        if opt.max_steps:
+            iters = min(iters, opt.max_steps)
+        bt, dtm = AverageMeter(), AverageMeter()
+        losses, top1, top5 = ([AverageMeter() for _ in range(G)] for _ in range(3))
+        win = torch.zeros(G, 4, dtype=torch.float64, device=self.device)   # per head: Σloss·b, Σacc1·b, Σacc5·b, Σb
+        end = time.time()
+        for idx_i, idx in enumerate(self.sampler.batches(self.device)):
+            if idx_i >= iters:
+                break
+            dtm.update(time.time() - end)
+            ph = self.prof.phase
+            with ph("augment"):
+                x = self.train.views(idx, self.aug_train, step_seed(opt.seed, epoch, idx_i, 0))
+                labels = self.train.labels[idx]
+            bsz = labels.shape[0]
+            self._set_head_lrs([warmup_lr(o, epoch, idx_i, iters) for o in self.head_opts])
+            with ph("encoder"):
+                feats = self.encode(x)
+            with ph("classifier"):
+                output, loss, acc1, acc5 = self._classify_sweep(feats, labels, True)
+                win += torch.stack([loss.double() * bsz, acc1.double() * bsz, acc5.double() * bsz,
+                                    torch.full((G,), float(bsz), dtype=torch.float64, device=self.device)], dim=1)
+            bt.update(time.time() - end)
+            if (idx_i + 1) % opt.print_freq == 0 or idx_i + 1 == iters:
+                # one host sync per print window: the sums and head 0's last batch together
+                host = torch.cat([win.flatten(), loss[:1].double(), acc1[:1].double()]).tolist()
+                win.zero_()
+                for g in range(G):
+                    sl, s1, s5, nb = host[4 * g:4 * g + 4]
+                    losses[g].update(sl / nb, nb)
+                    top1[g].update(s1 / nb, nb)
+                    top5[g].update(s5 / nb, nb)
+                losses[0].val, top1[0].val = host[4 * G], host[4 * G + 1]
+                logging.info("Train: [{0}][{1}/{2}]\tBT {bt.val:.3f} ({bt.avg:.3f})\t"
+                             "DT {dt.val:.3f} ({dt.avg:.3f})\tloss {loss.val:.3f} ({loss.avg:.3f})\t"
+                             "Acc@1 {top1.val:.3f} ({top1.avg:.3f}) [h0 of {3}]".format(
+                                 epoch, idx_i + 1, iters, G, bt=bt, dt=dtm, loss=losses[0], top1=top1[0]))
+                if self.prof.enabled:
+                    logging.info("phases (ms/step): " + PhaseTimer.format(self.prof.summary()))
+                sys.stdout.flush()
+            end = time.time()
+        return [m.avg for m in losses], [m.avg for m in top1], [m.avg for m in top5]
+
+    @torch.no_grad()
+    def _validate_sweep(self):
+        """``validate`` for G heads: per-head (loss, acc1, acc5) lists."""
+        opt = self.opt
+        G = len(self.sweep)
+        n = len(self.val)
+        losses, top1, top5 = ([AverageMeter() for _ in range(G)] for _ in range(3))
+        vb = opt.val_batch_size
+        for i, s in enumerate(range(0, n, vb)):
+            idx = torch.arange(s, min(s + vb, n), device=self.device)
+            x = self.val.views(idx, self.aug_val, 0)
+            labels = self.val.labels[idx]
+            output, loss, acc1, acc5 = self._classify_sweep(self.encode(x), labels, False)
+            bsz = labels.shape[0]
+            host = torch.stack([loss, acc1, acc5], dim=1).tolist()
+            for g in range(G):
+                losses[g].update(host[g][0], bsz)
+                top1[g].update(host[g][1], bsz)
+                top5[g].update(host[g][2], bsz)
+            if i % opt.print_freq == 0:
+                logging.info("Test: [{0}/{1}]\tLoss {loss.val:.4f} ({loss.avg:.4f})\t"
+                             "Acc@1 {top1.val:.3f} ({top1.avg:.3f}) [h0 of {2}]".format(
+                                 i, (n + vb - 1) // vb, G, loss=losses[0], top1=top1[0]))
+        for g in range(G):
+            logging.info(" * h{0} Acc@1 {top1.avg:.3f}, Acc@5 {top5.avg:.3f}".format(g, top1=top1[g], top5=top5[g]))
+        return [m.avg for m in losses], [m.avg for m in top1], [m.avg for m in top5]
+
+    def _run_sweep(self):
+        opt = self.opt
+        G = len(self.sweep)
+        res = [{"lr": lr, "wd": wd, "best_acc": 0.0, "best_acc5": 0.0, "best_epoch": 0} for lr, wd in self.sweep]
+        if getattr(opt, "knn", False):
+            self.knn_eval()
+        for epoch in range(1, opt.epochs + 1):
+            self._set_head_lrs([lr_at_epoch(o, epoch) for o in self.head_opts])
+            t1 = time.time()
+            loss, acc, acc5 = self.train_epoch(epoch)
+            logging.info("Train epoch {}, total time {:.2f}, accuracy:{}".format(
+                epoch, time.time() - t1, " ".join("{:.2f}".format(a) for a in acc)))
+            vloss, vacc, vacc5 = self.validate()
+            for g in range(G):
+                self.logger.log_value(f"classifier/train_loss/h{g}", loss[g], epoch)
+                self.logger.log_value(f"classifier/train_acc1/h{g}", acc[g], epoch)
+                self.logger.log_value(f"classifier/train_acc5/h{g}", acc5[g], epoch)
+                self.logger.log_value(f"classifier/val_loss/h{g}", vloss[g], epoch)
+                self.logger.log_value(f"classifier/val_acc1/h{g}", vacc[g], epoch)
+                self.logger.log_value(f"classifier/val_acc5/h{g}", vacc5[g], epoch)
+                if vacc[g] > res[g]["best_acc"]:
+                    res[g].update(best_acc=vacc[g], best_acc5=vacc5[g], best_epoch=epoch)
+        for g, r in enumerate(res):
+            logging.info("head {} lr {:g} wd {:g}: best accuracy {:.2f}, accuracy5 {:.2f}".format(
+                g, r["lr"], r["wd"], r["best_acc"], r["best_acc5"]))
+        best = max(res, key=lambda r: r["best_acc"])      # the first of equals
+        logging.info("best accuracy: {:.2f}, accuracy5: {:.2f}".format(best["best_acc"], best["best_acc5"]))
+        self.sweep_results = res
+        self.logger.close()
+        return best["best_acc"], best["best_acc5"]
 
     def _classify(self, feats, labels, train: bool):
         """(logits, loss, acc1, acc5) of a batch — device tensors; train: + the SGD step."""
@@ -99,6 +268,8 @@ class LinearEngine:
         return output, loss.detach(), acc1[0], acc5[0]
 
     def train_epoch(self, epoch):
+        if self.sweep:
+            return self._train_epoch_sweep(epoch)
         opt = self.opt
         self.classifier.train()
         self.sampler.set_epoch(epoch)
@@ -147,6 +318,8 @@ class LinearEngine:
 
     @torch.no_grad()
     def validate(self):
+        if self.sweep:
+            return self._validate_sweep()
         opt = self.opt
         self.classifier.eval()
         n = len(self.val)
@@ -182,6 +355,8 @@ class LinearEngine:
         return acc1, acc5
 
     def run(self):
+        if self.sweep:
+            return self._run_sweep()
         opt = self.opt
         best_acc, best_acc5 = 0.0, 0.0
         if getattr(opt, "knn", False):

@@ -10,10 +10,13 @@ networks/resnet_big.py:196-204).
 * :class:`NativeLinearCE` — ``LinearClassifier`` + ``CrossEntropyLoss`` + top-1/5 +
   ``torch.optim.SGD`` as two fused launches per batch (csrc/kernels/linear_ce.hip), fp32 as
   the reference classifier; the statistics stay on the device.
+* :class:`NativeLinearSweep` — G such classifiers, each with its own learning rate and weight
+  decay, on one feature batch in the same two launches (csrc/kernels/linear_ce_sweep.hip): a
+  hyper-parameter sweep of the probe pays for the encoder once.
 """
 from __future__ import annotations
 
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Sequence
 
 import torch
 
@@ -135,9 +138,56 @@ class NativeLinearCE:
         return out[0], out[1]
 
 
+SWEEP_MAX_HEADS = 16
+
+
+class NativeLinearSweep:
+    """G copies of a ``LinearClassifier`` trained side by side on the same features, head g
+    with its own learning rate and weight decay: two launches per batch for all of them
+    (csrc/kernels/linear_ce_sweep.hip). Every head starts from ``classifier``'s weights and is
+    bit-identical to a :class:`NativeLinearCE` run alone with its settings."""
+
+    def __init__(self, classifier: torch.nn.Module, weight_decays: Sequence[float], momentum: float = 0.9):
+        fc = classifier.fc
+        self.G = len(weight_decays)
+        if not 1 <= self.G <= SWEEP_MAX_HEADS:
+            raise ValueError(f"a sweep has 1..{SWEEP_MAX_HEADS} heads, got {self.G}")
+        self.W = fc.weight.detach().unsqueeze(0).repeat(self.G, 1, 1).contiguous()
+        self.b = fc.bias.detach().unsqueeze(0).repeat(self.G, 1).contiguous()
+        self.momentum = float(momentum)
+        self.weight_decays = [float(w) for w in weight_decays]
+        self.bufW = torch.zeros_like(self.W)
+        self.bufb = torch.zeros_like(self.b)
+        self.first = True
+
+    @torch.no_grad()
+    def train_batch(self, feats: torch.Tensor, labels: torch.Tensor, lrs: Sequence[float]):
+        """One SGD step of every head; returns (logits [G, B, C], stats [G, 3]) on device."""
+        out = _ext.require().linear_ce_sweep_step(feats.float().contiguous(), self.W, self.b, labels.long(),
+                                                  self.bufW, self.bufb, [float(v) for v in lrs], self.momentum,
+                                                  self.weight_decays, self.first, True)
+        self.first = False
+        return out[0], out[1]
+
+    @torch.no_grad()
+    def eval_batch(self, feats: torch.Tensor, labels: torch.Tensor):
+        zeros = [0.0] * self.G
+        out = _ext.require().linear_ce_sweep_step(feats.float().contiguous(), self.W, self.b, labels.long(),
+                                                  None, None, zeros, 0.0, zeros, False, False)
+        return out[0], out[1]
+
+    def head_state(self, g: int) -> Dict[str, torch.Tensor]:
+        """``LinearClassifier`` state dict of head ``g``."""
+        return {"fc.weight": self.W[g].clone(), "fc.bias": self.b[g].clone()}
+
+
 def supported(classifier: torch.nn.Module, feat_dim: Optional[int] = None) -> bool:
     fc = getattr(classifier, "fc", None)
     if fc is None or not fc.weight.is_cuda or not _ext.available():
         return False
     k, c = fc.in_features, fc.out_features
     return k % 64 == 0 and k <= 2048 and ((k // 64) & (k // 64 - 1)) == 0 and c <= 1024
+
+
+def sweep_supported(classifier: torch.nn.Module, G: int) -> bool:
+    return 1 <= G <= SWEEP_MAX_HEADS and supported(classifier)
