@@ -533,9 +533,120 @@ std::vector<torch::Tensor> block_bwd(torch::Tensor dout, std::vector<torch::Tens
   return {dx, prev_slab};
 }
 
+// ---- test-only bindings of the BN3 fold kernels (tests/bnfold_checks.py) -----------------
+// Thin wrappers over the launchers: every extent a kernel reads or writes is checked here,
+// the shape rules of the kernels themselves (which K and C they take) are left to the
+// launchers, whose hipErrorInvalidValue comes back as a RuntimeError before any launch.
+
+void check_f32(const torch::Tensor& t, int64_t numel, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat && t.is_contiguous() && t.numel() == numel, name,
+              " must be a contiguous float32 GPU tensor of ", numel, " elements");
+}
+
+void check_bf16_flat(const torch::Tensor& t, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kBFloat16 && t.is_contiguous(), name,
+              " must be a contiguous bf16 GPU tensor");
+}
+
+// w [C][1][1][K] bf16 -> (C, K)
+std::pair<int64_t, int64_t> fold_weight_dims(const torch::Tensor& w) {
+  check_bf16_flat(w, "w");
+  TORCH_CHECK(w.dim() == 4 && w.size(1) == 1 && w.size(2) == 1 && w.size(0) > 0 && w.size(3) > 0 &&
+                  w.size(0) < (1 << 20) && w.size(3) < (1 << 20),
+              "w must be [C][1][1][K]");
+  return {w.size(0), w.size(3)};
+}
+
+// Wd, Mx and b into caller-supplied (flat) outputs: wd_out holds rows of ldw elements (0: C),
+// mx_out rows of ldm (0: K); the concatenated layout is mx_out = wd_out[C:], ldw = ldm = C + K
+void bnfold_prep_test(torch::Tensor coef, torch::Tensor w, torch::Tensor wt, OptT mu, OptT cs, int64_t rows,
+                      int64_t ldw, int64_t ldm, torch::Tensor wd_out, torch::Tensor mx_out, torch::Tensor bias_out) {
+  const auto [C, K] = fold_weight_dims(w);
+  check_bf16_flat(wt, "wt");
+  TORCH_CHECK(wt.dim() == 4 && wt.size(0) == K && wt.size(1) == 1 && wt.size(2) == 1 && wt.size(3) == C,
+              "wt must be [K][1][1][C]");
+  check_f32(coef, 3 * C, "coef");
+  check_f32(bias_out, K, "bias_out");
+  check_bf16_flat(wd_out, "wd_out");
+  check_bf16_flat(mx_out, "mx_out");
+  TORCH_CHECK(rows >= 0 && rows < (1LL << 31) && ldw >= 0 && ldm >= 0 && ldw < (1 << 24) && ldm < (1 << 24),
+              "bnfold_prep: rows, ldw or ldm out of range");
+  const int64_t lw = ldw == 0 ? C : ldw, lm = ldm == 0 ? K : ldm;
+  TORCH_CHECK(wd_out.numel() >= (K - 1) * lw + C, "wd_out too small for K rows of ldw");
+  TORCH_CHECK(mx_out.numel() >= (K - 1) * lm + K, "mx_out too small for K rows of ldm");
+  const float* pmu = opt_ptr(mu, C, "mu");
+  const float* pcs = opt_ptr(cs, K, "cs");
+  c10::DeviceGuard dg(w.device());
+  check_hip(launch_bnfold_prep(coef.data_ptr<float>(), w.data_ptr(), wt.data_ptr(), (int)C, (int)K, wd_out.data_ptr(),
+                               mx_out.data_ptr(), bias_out.data_ptr<float>(), pmu, pcs, (long)rows, cur_stream(),
+                               (int)ldw, (int)ldm),
+            "bnfold_prep");
+}
+
+// x [rows][K] bf16 -> (cs [K], partial [bnfold_colsum_blocks()][K])
+std::vector<torch::Tensor> bnfold_colsum_test(torch::Tensor x, OptT partial) {
+  check_bf16_flat(x, "x");
+  TORCH_CHECK(x.dim() == 2 && x.size(1) > 0 && x.numel() < (1LL << 31), "x must be [rows][K] bf16");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0, "x must be 16-byte aligned");
+  const int64_t rows = x.size(0), K = x.size(1);
+  c10::DeviceGuard dg(x.device());
+  auto opt = x.options().dtype(at::kFloat);
+  const int64_t nb = bnfold_colsum_blocks();
+  torch::Tensor part = partial.has_value() && partial->defined() ? *partial : torch::empty({nb, K}, opt);
+  check_f32(part, nb * K, "partial");
+  auto cs = torch::empty({K}, opt);
+  check_hip(launch_bnfold_colsum(x.data_ptr(), (long)rows, (int)K, part.data_ptr<float>(), cs.data_ptr<float>(),
+                                 cur_stream()),
+            "bnfold_colsum");
+  return {cs, part};
+}
+
+// sink [C][K] (+)= diag(A)·G + diag(D)·W3·S + E ⊗ Σ_b cs[b]; returns the sink
+torch::Tensor bnfold_wgrad_test(torch::Tensor coef, torch::Tensor G, torch::Tensor S, torch::Tensor cs,
+                                torch::Tensor w, torch::Tensor sink, bool accumulate) {
+  const auto [C, K] = fold_weight_dims(w);
+  check_f32(coef, 3 * C, "coef");
+  check_f32(G, C * K, "G");
+  check_f32(S, K * K, "S");
+  check_f32(sink, C * K, "sink");
+  TORCH_CHECK(cs.dim() == 2 && cs.size(1) == K, "cs must be [ncs][K]");
+  check_f32(cs, cs.size(0) * K, "cs");
+  c10::DeviceGuard dg(w.device());
+  check_hip(launch_bnfold_wgrad(coef.data_ptr<float>(), G.data_ptr<float>(), S.data_ptr<float>(), cs.data_ptr<float>(),
+                                (int)cs.size(0), w.data_ptr(), (int)C, (int)K, sink.data_ptr<float>(),
+                                accumulate ? 1 : 0, cur_stream()),
+            "bnfold_wgrad");
+  return sink;
+}
+
+// Σ_k W[c][k]·G[c][k] as fp32 hi / lo into set 1 of out [2][ns][C]; returns out
+torch::Tensor bnfold_rowdot_test(torch::Tensor G, torch::Tensor w, int64_t ns, torch::Tensor out) {
+  const auto [C, K] = fold_weight_dims(w);
+  check_f32(G, C * K, "G");
+  TORCH_CHECK(ns >= 0 && ns <= 16 && out.dim() == 3 && out.size(0) == 2 && out.size(1) == ns && out.size(2) == C,
+              "out must be [2][ns][C]");
+  check_f32(out, 2 * ns * C, "out");
+  c10::DeviceGuard dg(w.device());
+  check_hip(launch_bnfold_rowdot(G.data_ptr<float>(), w.data_ptr(), (int)C, (int)K, (int)ns, out.data_ptr<float>(),
+                                 cur_stream()),
+            "bnfold_rowdot");
+  return out;
+}
+
 }  // namespace
 
 void register_block(pybind11::module& m) {
+  m.def("bnfold_prep", &bnfold_prep_test, "BN3 fold (test only): Wd, Mx and b into caller-supplied outputs",
+        pybind11::arg("coef"), pybind11::arg("w"), pybind11::arg("wt"), pybind11::arg("mu") = pybind11::none(),
+        pybind11::arg("cs") = pybind11::none(), pybind11::arg("rows") = 0, pybind11::arg("ldw") = 0,
+        pybind11::arg("ldm") = 0, pybind11::arg("wd_out"), pybind11::arg("mx_out"), pybind11::arg("bias_out"));
+  m.def("bnfold_colsum", &bnfold_colsum_test, "BN3 fold (test only): column sums of x [rows][K] -> (cs, partial)",
+        pybind11::arg("x"), pybind11::arg("partial") = pybind11::none());
+  m.def("bnfold_wgrad", &bnfold_wgrad_test, "BN3 fold (test only): the folded weight gradient into sink",
+        pybind11::arg("coef"), pybind11::arg("G"), pybind11::arg("S"), pybind11::arg("cs"), pybind11::arg("w"),
+        pybind11::arg("sink"), pybind11::arg("accumulate"));
+  m.def("bnfold_rowdot", &bnfold_rowdot_test, "BN3 fold (test only): Σ_k W·G as fp32 hi / lo slab rows",
+        pybind11::arg("G"), pybind11::arg("w"), pybind11::arg("ns"), pybind11::arg("out"));
   m.def("side_stash_release", [] { side_stash().clear(); },
         "drop the tensors kept alive for side-stream wgrads (after join)");
   m.def("block_fwd", &block_fwd, "native residual-block forward (whole kernel sequence; comm: SyncBN handle or 0)",
