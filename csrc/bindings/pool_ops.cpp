@@ -11,11 +11,17 @@ void check_nhwc(const torch::Tensor& t, const char* name) {
               name, " must be a contiguous NHWC bf16 GPU tensor with C % 8 == 0");
 }
 
+// before anything divides by stride
+void check_window(int64_t k, int64_t stride, int64_t pad) {
+  TORCH_CHECK(k >= 1 && stride >= 1 && pad >= 0 && pad < k, "bad pool geometry: k >= 1, stride >= 1, 0 <= pad < k");
+}
+
 torch::Tensor maxpool_fwd(torch::Tensor x, int64_t k, int64_t stride, int64_t pad) {
   check_nhwc(x, "x");
+  check_window(k, stride, pad);
   const int64_t N = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3);
+  TORCH_CHECK(H + 2 * pad >= k && W + 2 * pad >= k, "bad pool geometry: the window exceeds the padded image");
   const int64_t P = (H + 2 * pad - k) / stride + 1, Q = (W + 2 * pad - k) / stride + 1;
-  TORCH_CHECK(P > 0 && Q > 0 && pad < k, "bad pool geometry");
   c10::DeviceGuard dg(x.device());
   auto y = torch::empty({N, P, Q, C}, x.options());
   check_hip(launch_maxpool_fwd(x.data_ptr(), y.data_ptr(), N, H, W, C, P, Q, k, stride, pad, cur_stream()),
@@ -28,6 +34,11 @@ torch::Tensor maxpool_bwd(torch::Tensor x, torch::Tensor y, torch::Tensor dy, in
   check_nhwc(y, "y");
   check_nhwc(dy, "dy");
   TORCH_CHECK(y.sizes() == dy.sizes(), "y/dy shape");
+  check_window(k, stride, pad);
+  const int64_t H = x.size(1), W = x.size(2);
+  TORCH_CHECK(H + 2 * pad >= k && W + 2 * pad >= k && y.size(0) == x.size(0) && y.size(3) == x.size(3) &&
+                  y.size(1) == (H + 2 * pad - k) / stride + 1 && y.size(2) == (W + 2 * pad - k) / stride + 1,
+              "maxpool_bwd: y / dy must be [N, P, Q, C] of x's N and C and the pool geometry");
   c10::DeviceGuard dg(x.device());
   auto dx = torch::empty_like(x);
   check_hip(launch_maxpool_bwd(x.data_ptr(), y.data_ptr(), dy.data_ptr(), dx.data_ptr(), x.size(0), x.size(1),
@@ -39,9 +50,11 @@ torch::Tensor maxpool_bwd(torch::Tensor x, torch::Tensor y, torch::Tensor dy, in
 // max-pool forward + per-window first-max positions (uint8, same shape as y)
 std::vector<torch::Tensor> maxpool_fwd_idx(torch::Tensor x, int64_t k, int64_t stride, int64_t pad) {
   check_nhwc(x, "x");
+  check_window(k, stride, pad);
   const int64_t N = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3);
+  TORCH_CHECK(H + 2 * pad >= k && W + 2 * pad >= k && k * k <= 255,
+              "bad pool geometry: the window exceeds the padded image, or k > 15");
   const int64_t P = (H + 2 * pad - k) / stride + 1, Q = (W + 2 * pad - k) / stride + 1;
-  TORCH_CHECK(P > 0 && Q > 0 && pad < k && k * k <= 255, "bad pool geometry");
   c10::DeviceGuard dg(x.device());
   auto y = torch::empty({N, P, Q, C}, x.options());
   auto idx = torch::empty({N, P, Q, C}, x.options().dtype(at::kByte));
@@ -57,7 +70,9 @@ torch::Tensor maxpool_bwd_idx(torch::Tensor idx, torch::Tensor dy, int64_t H, in
   check_nhwc(dy, "dy");
   TORCH_CHECK(idx.is_cuda() && idx.scalar_type() == at::kByte && idx.is_contiguous() && idx.sizes() == dy.sizes(),
               "idx: contiguous uint8 of dy's shape");
-  TORCH_CHECK((H + 2 * pad - k) / stride + 1 == dy.size(1) && (W + 2 * pad - k) / stride + 1 == dy.size(2),
+  check_window(k, stride, pad);
+  TORCH_CHECK(H + 2 * pad >= k && W + 2 * pad >= k && k * k <= 255 &&
+                  (H + 2 * pad - k) / stride + 1 == dy.size(1) && (W + 2 * pad - k) / stride + 1 == dy.size(2),
               "pool geometry mismatch");
   c10::DeviceGuard dg(dy.device());
   auto dx = torch::empty({dy.size(0), H, W, dy.size(3)}, dy.options());

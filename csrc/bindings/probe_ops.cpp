@@ -65,6 +65,39 @@ std::vector<torch::Tensor> linear_ce_step(torch::Tensor x, torch::Tensor W, torc
   return {logits, stats};
 }
 
+// Test-only: linear_ce_step's second launch alone, on a caller-supplied dz [B][C] and rowstat
+// [B][3] (tests/test_gpu_aux_oracle.py feeds it integers, where every sum is exact). Updates W,
+// b, bufW, bufb in place (contiguous fp32, views of a larger buffer allowed); returns stats [3].
+torch::Tensor linear_ce_sgd_raw(torch::Tensor x, torch::Tensor dz, torch::Tensor W, torch::Tensor b,
+                                torch::Tensor bufW, torch::Tensor bufb, double lr, double momentum, double wd,
+                                bool first, torch::Tensor rowstat) {
+  TORCH_CHECK(x.dim() == 2 && W.dim() == 2, "x [B][K], W [C][K]");
+  const int64_t B = x.size(0), K = x.size(1), C = W.size(0);
+  check_f32(x, {B, K}, "x");
+  check_f32(W, {C, K}, "W");
+  check_f32(b, {C}, "b");
+  check_f32(dz, {B, C}, "dz");
+  check_f32(bufW, {C, K}, "bufW");
+  check_f32(bufb, {C}, "bufb");
+  check_f32(rowstat, {B, 3}, "rowstat");
+  TORCH_CHECK(B >= 1 && linear_ce_supported((int)K, (int)C) && ((K / 64) & (K / 64 - 1)) == 0,
+              "linear_ce: K = 64·2^j <= 2048, C <= 1024");
+  TORCH_CHECK(B * C < (1LL << 31) && B * K < (1LL << 31), "linear_ce: sizes");
+  const int dev = x.get_device();
+  for (const torch::Tensor* t : {&dz, &W, &b, &bufW, &bufb, &rowstat})
+    TORCH_CHECK(t->get_device() == dev, "linear_ce_sgd_raw: one device");
+  auto aligned = [](const torch::Tensor& t) { return reinterpret_cast<uintptr_t>(t.data_ptr<float>()) % 16 == 0; };
+  TORCH_CHECK(aligned(x) && aligned(W) && aligned(bufW), "linear_ce_sgd_raw: x, W and bufW must be 16-byte aligned");
+  c10::DeviceGuard dg(x.device());
+  auto stats = torch::empty({3}, x.options());
+  check_hip(launch_linear_ce_sgd(x.data_ptr<float>(), dz.data_ptr<float>(), (int)B, (int)K, (int)C,
+                                 W.data_ptr<float>(), b.data_ptr<float>(), bufW.data_ptr<float>(),
+                                 bufb.data_ptr<float>(), (float)lr, (float)momentum, (float)wd, first ? 1 : 0,
+                                 rowstat.data_ptr<float>(), stats.data_ptr<float>(), cur_stream()),
+            "linear_ce_sgd_raw");
+  return stats;
+}
+
 // One batch of a hyper-parameter sweep (linear_ce_sweep.hip): G classifiers W [G][C][K], b [G][C]
 // on the same features x [B][K], head g with lrs[g] / wds[g]; momentum and `first` are shared.
 // train: bufW [G][C][K], bufb [G][C]; eval: no buffers. Views of larger tensors are allowed when
@@ -207,6 +240,11 @@ void register_probe(pybind11::module& m) {
         pybind11::arg("x"), pybind11::arg("W"), pybind11::arg("b"), pybind11::arg("labels"), pybind11::arg("bufW"),
         pybind11::arg("bufb"), pybind11::arg("lr"), pybind11::arg("momentum"), pybind11::arg("wd"),
         pybind11::arg("first"), pybind11::arg("train"));
+  m.def("linear_ce_sgd_raw", &linear_ce_sgd_raw,
+        "test-only: the gradient + SGD launch of linear_ce_step on a caller-supplied dz and rowstat -> stats [3]",
+        pybind11::arg("x"), pybind11::arg("dz"), pybind11::arg("W"), pybind11::arg("b"), pybind11::arg("bufW"),
+        pybind11::arg("bufb"), pybind11::arg("lr"), pybind11::arg("momentum"), pybind11::arg("wd"),
+        pybind11::arg("first"), pybind11::arg("rowstat"));
   m.def("linear_ce_sweep_step", &linear_ce_sweep_step,
         "G linear classifiers with per-head lr / wd on one feature batch: logits [G][B][C], stats [G][3] "
         "(+ gradients and SGD updates when train); head g is bit-identical to linear_ce_step",

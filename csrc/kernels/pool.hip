@@ -5,6 +5,8 @@
 //   activations 16x). Backward recomputes the window argmax from the saved input and
 //   gathers: every input element sums the gradients of the windows whose max it is
 //   (first max in scan order, as torch) — no index tensor stored, no atomics.
+//   Padding counts as -inf; ±inf inputs are handled, a NaN input is outside the contract
+//   (the comparisons drop it, and the two backwards need not agree on its window).
 // * global average pool forward (fp32 [N, C] out) and backward (broadcast dy/HW).
 // Vectorised over 8 channels (16-B loads) per lane.
 #include "common.h"
@@ -45,10 +47,13 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const uint16_t* __rest
     const int n = (int)(r / g.P);
     float m[8];
     int at[8];
+    // the first tap of the window inside the image (pad < k: there is one): a window whose
+    // taps are all -inf names it, as the recomputing backward and torch do, not a padded tap
+    const int at0 = max(0, g.pad - p * g.stride) * g.k + max(0, g.pad - q * g.stride);
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       m[i] = -INFINITY;
-      at[i] = 0;
+      at[i] = at0;
     }
     for (int dy = 0; dy < g.k; ++dy) {
       const int yy = p * g.stride - g.pad + dy;
