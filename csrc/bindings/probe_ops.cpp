@@ -224,9 +224,186 @@ c10::optional<torch::Tensor> ce_head_bwd(torch::Tensor x, torch::Tensor dz, torc
   return dX;
 }
 
+// ---- the MFMA classifier head (head_gemm.hip): the same ops on bf16x3 GEMMs ---------------
+// Same argument lists and return tuples as their FMA siblings above; the wider range
+// (K = 64·j <= 4096, C <= 32768) is checked by head_gemm_supported.
+
+bool aligned16(const torch::Tensor& t) { return reinterpret_cast<uintptr_t>(t.data_ptr<float>()) % 16 == 0; }
+
+void check_labels(const torch::Tensor& labels, int64_t B, int dev) {
+  TORCH_CHECK(labels.is_cuda() && labels.scalar_type() == at::kLong && labels.numel() == B && labels.is_contiguous() &&
+                  labels.get_device() == dev,
+              "labels: int64 [B] on x's device");
+}
+
+// W [G][C][K] or its single-head [C][K] form (heads = false); everything checked before any
+// allocation or launch
+std::vector<torch::Tensor> head_gemm_step(const char* op, bool heads, torch::Tensor x, torch::Tensor W,
+                                          torch::Tensor b, torch::Tensor labels, OptT bufW, OptT bufb,
+                                          const std::vector<double>& lrs, double momentum,
+                                          const std::vector<double>& wds, bool first, bool train) {
+  TORCH_CHECK(x.dim() == 2 && W.dim() == (heads ? 3 : 2), op, ": x [B][K], W ", heads ? "[G][C][K]" : "[C][K]");
+  const int64_t B = x.size(0), K = x.size(1), G = heads ? W.size(0) : 1, C = W.size(heads ? 1 : 0);
+  TORCH_CHECK(G >= 1 && G <= kLinearSweepMaxHeads, op, ": 1 <= G <= ", kLinearSweepMaxHeads, ", got ", G);
+  TORCH_CHECK((int64_t)lrs.size() == G && (int64_t)wds.size() == G, op, ": ", G, " heads need ", G,
+              " learning rates and weight decays, got ", lrs.size(), " and ", wds.size());
+  const std::vector<int64_t> wshape = heads ? std::vector<int64_t>{G, C, K} : std::vector<int64_t>{C, K};
+  const std::vector<int64_t> bshape = heads ? std::vector<int64_t>{G, C} : std::vector<int64_t>{C};
+  check_f32(x, {B, K}, "x");
+  check_f32(W, wshape, "W");
+  check_f32(b, bshape, "b");
+  const int dev = x.get_device();
+  check_labels(labels, B, dev);
+  TORCH_CHECK(B >= 1 && B < (1LL << 31) && head_gemm_supported((int)G, (int)B, (int)K, (int)C), op,
+              ": K % 64 == 0, 64 <= K <= 4096, 1 <= C <= 32768, B >= 1, element counts below 2^31");
+  TORCH_CHECK(aligned16(x) && aligned16(W), op, ": x and W must be 16-byte aligned");
+  TORCH_CHECK(W.get_device() == dev && b.get_device() == dev, op, ": one device");
+  if (train) {
+    TORCH_CHECK(bufW.has_value() && bufb.has_value(), "momentum buffers required for a training step");
+    check_f32(*bufW, wshape, "bufW");
+    check_f32(*bufb, bshape, "bufb");
+    TORCH_CHECK(bufW->get_device() == dev && bufb->get_device() == dev, op, ": one device");
+    TORCH_CHECK(aligned16(*bufW), op, ": bufW must be 16-byte aligned");
+  }
+  c10::DeviceGuard dg(x.device());
+  auto fo = x.options();
+  auto logits = heads ? torch::empty({G, B, C}, fo) : torch::empty({B, C}, fo);
+  auto rowstat = torch::empty({G, B, 3}, fo);
+  auto stats = heads ? torch::empty({G, 3}, fo) : torch::empty({3}, fo);
+  torch::Tensor dz;
+  if (train) dz = torch::empty({G, B, C}, fo);
+  float lr[kLinearSweepMaxHeads], wd[kLinearSweepMaxHeads];
+  for (int64_t g = 0; g < G; ++g) {
+    lr[g] = (float)lrs[g];
+    wd[g] = (float)wds[g];
+  }
+  check_hip(launch_head_gemm_logits(x.data_ptr<float>(), W.data_ptr<float>(), b.data_ptr<float>(),
+                                    labels.data_ptr<int64_t>(), (int)G, (int)B, (int)K, (int)C, (float)(1.0 / B),
+                                    logits.data_ptr<float>(), train ? dz.data_ptr<float>() : nullptr,
+                                    rowstat.data_ptr<float>(), cur_stream()),
+            op);
+  if (train)
+    check_hip(launch_head_gemm_sgd(x.data_ptr<float>(), dz.data_ptr<float>(), (int)G, (int)B, (int)K, (int)C,
+                                   W.data_ptr<float>(), b.data_ptr<float>(), bufW->data_ptr<float>(),
+                                   bufb->data_ptr<float>(), lr, wd, (float)momentum, first ? 1 : 0,
+                                   rowstat.data_ptr<float>(), stats.data_ptr<float>(), cur_stream()),
+              op);
+  else
+    check_hip(launch_head_gemm_stats((int)G, (int)B, (int)K, (int)C, rowstat.data_ptr<float>(),
+                                     stats.data_ptr<float>(), nullptr, cur_stream()),
+              op);
+  return {logits, stats};
+}
+
+std::vector<torch::Tensor> linear_ce_step_mfma(torch::Tensor x, torch::Tensor W, torch::Tensor b,
+                                               torch::Tensor labels, OptT bufW, OptT bufb, double lr, double momentum,
+                                               double wd, bool first, bool train) {
+  return head_gemm_step("linear_ce_step_mfma", false, x, W, b, labels, bufW, bufb, {lr}, momentum, {wd}, first,
+                        train);
+}
+
+std::vector<torch::Tensor> linear_ce_sweep_step_mfma(torch::Tensor x, torch::Tensor W, torch::Tensor b,
+                                                     torch::Tensor labels, OptT bufW, OptT bufb,
+                                                     std::vector<double> lrs, double momentum, std::vector<double> wds,
+                                                     bool first, bool train) {
+  return head_gemm_step("linear_ce_sweep_step_mfma", true, x, W, b, labels, bufW, bufb, lrs, momentum, wds, first,
+                        train);
+}
+
+void check_head_gemm_classifier(const char* op, const torch::Tensor& x, const torch::Tensor& W) {
+  TORCH_CHECK(x.dim() == 2 && W.dim() == 2, op, ": x [B][K], W [C][K]");
+  const int64_t B = x.size(0), K = x.size(1), C = W.size(0);
+  check_f32(x, {B, K}, "x");
+  check_f32(W, {C, K}, "W");
+  TORCH_CHECK(B >= 1 && B < (1LL << 31) && head_gemm_supported(1, (int)B, (int)K, (int)C), op,
+              ": K % 64 == 0, 64 <= K <= 4096, 1 <= C <= 32768, B >= 1, element counts below 2^31");
+  TORCH_CHECK(aligned16(x) && aligned16(W) && W.get_device() == x.get_device(), op,
+              ": x and W 16-byte aligned on one device");
+}
+
+std::vector<torch::Tensor> ce_head_fwd_mfma(torch::Tensor x, torch::Tensor W, torch::Tensor b, torch::Tensor labels,
+                                            bool reduce) {
+  const char* op = "ce_head_fwd_mfma";
+  check_head_gemm_classifier(op, x, W);
+  const int64_t B = x.size(0), K = x.size(1), C = W.size(0);
+  check_f32(b, {C}, "b");
+  TORCH_CHECK(b.get_device() == x.get_device(), op, ": one device");
+  check_labels(labels, B, x.get_device());
+  c10::DeviceGuard dg(x.device());
+  auto fo = x.options();
+  auto logits = torch::empty({B, C}, fo);
+  auto dz = torch::empty({B, C}, fo);
+  auto rowstat = torch::empty({B, 3}, fo);
+  auto stats = torch::empty({3}, fo);
+  auto loss = torch::empty({}, fo);
+  check_hip(launch_head_gemm_logits(x.data_ptr<float>(), W.data_ptr<float>(), b.data_ptr<float>(),
+                                    labels.data_ptr<int64_t>(), 1, (int)B, (int)K, (int)C, (float)(1.0 / B),
+                                    logits.data_ptr<float>(), dz.data_ptr<float>(), rowstat.data_ptr<float>(),
+                                    cur_stream()),
+            op);
+  if (reduce)
+    check_hip(launch_head_gemm_stats(1, (int)B, (int)K, (int)C, rowstat.data_ptr<float>(), stats.data_ptr<float>(),
+                                     loss.data_ptr<float>(), cur_stream()),
+              op);
+  return {logits, dz, rowstat, stats, loss};
+}
+
+c10::optional<torch::Tensor> ce_head_bwd_mfma(torch::Tensor x, torch::Tensor dz, torch::Tensor W, torch::Tensor gout,
+                                              torch::Tensor rowstat, torch::Tensor stats, torch::Tensor loss, OptT dW,
+                                              OptT db, bool need_dx) {
+  const char* op = "ce_head_bwd_mfma";
+  check_head_gemm_classifier(op, x, W);
+  const int64_t B = x.size(0), K = x.size(1), C = W.size(0);
+  const int dev = x.get_device();
+  check_f32(dz, {B, C}, "dz");
+  check_f32(rowstat, {B, 3}, "rowstat");
+  check_f32(stats, {3}, "stats");
+  check_f32(loss, {}, "loss");
+  TORCH_CHECK(gout.is_cuda() && gout.scalar_type() == at::kFloat && gout.numel() == 1, "gout: one fp32 GPU value");
+  for (const torch::Tensor* t : {&dz, &rowstat, &stats, &loss, &gout})
+    TORCH_CHECK(t->get_device() == dev, op, ": one device");
+  TORCH_CHECK(aligned16(dz), op, ": dz must be 16-byte aligned");
+  TORCH_CHECK(dW.has_value() == db.has_value(), op, ": dW and db come together");
+  if (dW.has_value()) {
+    check_f32(*dW, {C, K}, "dW");
+    check_f32(*db, {C}, "db");
+    TORCH_CHECK(dW->get_device() == dev && db->get_device() == dev, "dW / db: x's device");
+    TORCH_CHECK(aligned16(*dW), "dW must be 16-byte aligned");
+  }
+  TORCH_CHECK(need_dx || dW.has_value(), op, ": nothing to compute");
+  c10::DeviceGuard dg(x.device());
+  c10::optional<torch::Tensor> dX;
+  if (need_dx) dX = torch::empty({B, K}, x.options());
+  check_hip(launch_head_gemm_bwd(x.data_ptr<float>(), dz.data_ptr<float>(), W.data_ptr<float>(), (int)B, (int)K,
+                                 (int)C, gout.data_ptr<float>(), need_dx ? dX->data_ptr<float>() : nullptr,
+                                 dW.has_value() ? dW->data_ptr<float>() : nullptr,
+                                 db.has_value() ? db->data_ptr<float>() : nullptr, rowstat.data_ptr<float>(),
+                                 stats.data_ptr<float>(), loss.data_ptr<float>(), cur_stream()),
+            op);
+  return dX;
+}
+
 }  // namespace
 
 void register_probe(pybind11::module& m) {
+  m.def("linear_ce_step_mfma", &linear_ce_step_mfma,
+        "linear_ce_step on bf16x3 MFMA GEMMs (head_gemm.hip): K = 64·j <= 4096, C <= 32768",
+        pybind11::arg("x"), pybind11::arg("W"), pybind11::arg("b"), pybind11::arg("labels"), pybind11::arg("bufW"),
+        pybind11::arg("bufb"), pybind11::arg("lr"), pybind11::arg("momentum"), pybind11::arg("wd"),
+        pybind11::arg("first"), pybind11::arg("train"));
+  m.def("linear_ce_sweep_step_mfma", &linear_ce_sweep_step_mfma,
+        "linear_ce_sweep_step on bf16x3 MFMA GEMMs; head g is bit-identical to linear_ce_step_mfma",
+        pybind11::arg("x"), pybind11::arg("W"), pybind11::arg("b"), pybind11::arg("labels"), pybind11::arg("bufW"),
+        pybind11::arg("bufb"), pybind11::arg("lrs"), pybind11::arg("momentum"), pybind11::arg("wds"),
+        pybind11::arg("first"), pybind11::arg("train"));
+  m.def("ce_head_fwd_mfma", &ce_head_fwd_mfma, "ce_head_fwd on bf16x3 MFMA GEMMs", pybind11::arg("x"),
+        pybind11::arg("W"), pybind11::arg("b"), pybind11::arg("labels"), pybind11::arg("reduce"));
+  m.def("ce_head_bwd_mfma", &ce_head_bwd_mfma, "ce_head_bwd on bf16x3 MFMA GEMMs", pybind11::arg("x"),
+        pybind11::arg("dz"), pybind11::arg("W"), pybind11::arg("gout"), pybind11::arg("rowstat"),
+        pybind11::arg("stats"), pybind11::arg("loss"), pybind11::arg("dW"), pybind11::arg("db"),
+        pybind11::arg("need_dx"));
+  m.def("head_gemm_supported", &head_gemm_supported, "whether the MFMA classifier head runs (G, B, K, C)",
+        pybind11::arg("G"), pybind11::arg("B"), pybind11::arg("K"), pybind11::arg("C"));
   m.def("ce_head_fwd", &ce_head_fwd,
         "trainable classifier + mean cross-entropy, forward: logits, dz, row statistics (+ their sums when reduce)",
         pybind11::arg("x"), pybind11::arg("W"), pybind11::arg("b"), pybind11::arg("labels"), pybind11::arg("reduce"));

@@ -35,6 +35,31 @@ hipError_t launch_ce_head_bwd(const float* x, const float* dz, const float* W, i
                               float* dX, float* dW, float* db, const float* rowstat, float* stats, float* loss,
                               hipStream_t s);
 
+// ---- MFMA classifier head (head_gemm.hip, head_gemm_plan.h): bf16x3 GEMMs -------------
+// The probe (G = 1), the sweep and the CE head on split-bf16 MFMA GEMMs. Layouts as the FMA
+// kernels: W [G][C][K], bias [G][C], logits / dz [G][B][C], rowstat [G][B][3], stats [G][3].
+// Supported: 1 <= G <= 16, K % 64 == 0 and 64 <= K <= 4096, 1 <= C <= 32768, B >= 1, every
+// element count below 2^31, x / W / bufW / dX / dW 16-byte aligned; everything else is
+// hipErrorInvalidValue before any launch.
+bool head_gemm_supported(int G, int B, int K, int C);
+// 2 launches: logits = x·Wᵀ + bias, then the row softmax: dz = (softmax − onehot)·gscale
+// (optional), rowstat
+hipError_t launch_head_gemm_logits(const float* x, const float* W, const float* bias, const int64_t* labels, int G,
+                                   int B, int K, int C, float gscale, float* logits, float* dz, float* rowstat,
+                                   hipStream_t s);
+// 1 launch: stats [G][3] = Σ_rows rowstat (fp64, row order); loss (optional, G = 1) = stats[0] / B
+hipError_t launch_head_gemm_stats(int G, int B, int K, int C, const float* rowstat, float* stats, float* loss,
+                                  hipStream_t s);
+// 1 launch: weight gradients + in-place SGD of every head (lrs / wds: G host values), biases and stats
+hipError_t launch_head_gemm_sgd(const float* x, const float* dz, int G, int B, int K, int C, float* W, float* bias,
+                                float* bufW, float* bufb, const float* lrs, const float* wds, float mom, int first,
+                                const float* rowstat, float* stats, hipStream_t s);
+// <= 2 launches: dX = gout·dz·W (optional), dW += gout·dzᵀ·x and db += gout·Σ_b dz (optional, both or
+// neither, at least one of dX / dW), stats, loss
+hipError_t launch_head_gemm_bwd(const float* x, const float* dz, const float* W, int B, int K, int C,
+                                const float* gout, float* dX, float* dW, float* db, const float* rowstat,
+                                float* stats, float* loss, hipStream_t s);
+
 // ---- linear-probe sweep: G classifiers on one feature batch (linear_ce_sweep.hip) ----
 // W [G][C][K], bias [G][C], buffers alike, logits / dz [G][B][C], rowstat [G][B][3], stats [G][3].
 // Supported: 1 <= G <= 16, K = 64·2^j <= 2048, 1 <= C <= 1024, B >= 1, G·B·C, B·K and G·C·K

@@ -321,11 +321,25 @@ def linear_parser() -> argparse.ArgumentParser:
                         "one per (lr, wd) pair, at most 16) and report the best")
     g.add_argument("--sweep_wd", type=float, nargs="+", default=None, metavar="WD",
                    help="weight decays of the sweep (absent: --weight_decay)")
+    _add_head_gemm_flag(g)
     _add_common_new_flags(p)
     return p
 
 
 SWEEP_MAX_HEADS = 16
+
+
+class _HeadOptions(argparse.Namespace):
+    """``opt.head_gemm`` reads "fma" when the flag is absent without becoming an entry of
+    ``vars(opt)``: a run that does not use the flag keeps the namespace (and the saved options) it
+    had before the flag existed."""
+    head_gemm = "fma"
+
+
+def _add_head_gemm_flag(g):
+    g.add_argument("--head_gemm", type=str, default=argparse.SUPPRESS, choices=["fma", "mfma"],
+                   help="classifier GEMMs: fma = the fp32 kernels (K = 64·2^j <= 2048, C <= 1024), mfma = split-bf16 "
+                        "MFMA GEMMs (csrc/kernels/head_gemm.hip: K = 64·j <= 4096, C <= 32768); default fma")
 
 
 def _sweep_heads(parser, opt):
@@ -365,7 +379,7 @@ def sweep_head_opts(opt):
 def parse_linear(argv: Optional[Sequence[str]] = None, make_dirs: bool = True,
                  now: Optional[datetime.datetime] = None):
     parser = linear_parser()
-    opt = parser.parse_args(argv)
+    opt = parser.parse_args(argv, namespace=_HeadOptions())
     _sweep_heads(parser, opt)
     if opt.knn_k < 1 or not opt.knn_t > 0:
         raise ValueError("--knn_k >= 1 and --knn_t > 0 are required")
@@ -456,13 +470,14 @@ def ce_parser() -> argparse.ArgumentParser:
     g.add_argument("--blur_kernel", type=int, default=0, help="blur kernel size, odd (0 = automatic)")
     g.add_argument("--blur_sigma", type=float, nargs=2, default=[0.1, 2.0], metavar=("LO", "HI"))
     _add_eval_flags(g)
+    _add_head_gemm_flag(g)
     _add_common_new_flags(p)
     return p
 
 
 def parse_ce(argv: Optional[Sequence[str]] = None, make_dirs: bool = True,
              now: Optional[datetime.datetime] = None):
-    opt = ce_parser().parse_args(argv)
+    opt = ce_parser().parse_args(argv, namespace=_HeadOptions())
     if opt.cuda_graph or opt.micro_batch:
         raise ValueError("main_ce.py supports neither --cuda_graph nor --micro_batch")
     if not 0.0 < opt.label_frac <= 1.0:

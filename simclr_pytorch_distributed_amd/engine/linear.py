@@ -78,8 +78,19 @@ class LinearEngine:
         self.encode, _ = linear_probe.eval_encoder(model, self.backend, self.runner)
         self.folded = self.encode if self.backend == "native" else None      # the FoldedEncoder, when there is one
         self.native_ce = None
-        if self.backend == "native" and linear_probe.supported(self.classifier):
-            self.native_ce = linear_probe.NativeLinearCE(self.classifier, opt.momentum, opt.weight_decay)
+        # --head_gemm mfma: the classifier GEMMs on head_gemm.hip where they can run, else the
+        # path of the default (fma) with one warning
+        self.head_gemm = getattr(opt, "head_gemm", "fma")
+        n_heads = len(getattr(opt, "sweep", None) or [None])
+        if self.head_gemm == "mfma" and not (self.backend == "native" and
+                                             linear_probe.sweep_supported(self.classifier, n_heads, gemm="mfma")):
+            logging.warning("--head_gemm mfma cannot run here (backend %s, device %s, %d x %d classifier, %d heads): "
+                            "using the fma path", self.backend, dev, self.classifier.fc.in_features,
+                            self.classifier.fc.out_features, n_heads)
+            self.head_gemm = "fma"
+        if self.backend == "native" and linear_probe.supported(self.classifier, gemm=self.head_gemm):
+            self.native_ce = linear_probe.NativeLinearCE(self.classifier, opt.momentum, opt.weight_decay,
+                                                         gemm=self.head_gemm)
         self.criterion = torch.nn.CrossEntropyLoss()
         self.optimizer = torch.optim.SGD(self.classifier.parameters(), lr=opt.learning_rate, momentum=opt.momentum,
                                          weight_decay=opt.weight_decay)
@@ -92,8 +103,10 @@ class LinearEngine:
             self.head_opts = sweep_head_opts(opt)
             self.head_lrs = [lr for lr, _ in self.sweep]
             wds = [wd for _, wd in self.sweep]
-            if self.backend == "native" and linear_probe.sweep_supported(self.classifier, len(self.sweep)):
-                self.native_sweep = linear_probe.NativeLinearSweep(self.classifier, wds, opt.momentum)
+            if self.backend == "native" and linear_probe.sweep_supported(self.classifier, len(self.sweep),
+                                                                         gemm=self.head_gemm):
+                self.native_sweep = linear_probe.NativeLinearSweep(self.classifier, wds, opt.momentum,
+                                                                   gemm=self.head_gemm)
             else:
                 self.classifiers = [copy.deepcopy(self.classifier) for _ in self.sweep]
                 self.optimizers = [torch.optim.SGD(c.parameters(), lr=lr, momentum=opt.momentum, weight_decay=wd)

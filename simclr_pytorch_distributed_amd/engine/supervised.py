@@ -37,6 +37,7 @@ from ..data.sampler import DistributedIndexSampler, label_subset
 from ..data.store import probe_stores
 from ..models.resnet import SupCEResNet
 from ..ops import _ext, linear_probe
+from ..ops import ce_head
 from ..ops.ce_head import classifier_ce
 from ..parallel import comm
 from ..utils.meters import AverageMeter
@@ -103,6 +104,20 @@ class SupervisedEngine(TrainEngine):
     def _init_state(self):
         self._syncbn_pending = False      # (no transport measurement in this trainer)
         self.history = []          # one dict per finished epoch (train / validation figures)
+        self._head_gemm = None     # decided at the first step, when the model sits on its device
+
+    def head_gemm(self) -> str:
+        """--head_gemm where it can run; else the default path, with one warning line."""
+        if self._head_gemm is None:
+            want = getattr(self.opt, "head_gemm", "fma")
+            fc = self.model.fc
+            if want == "mfma" and not (self.backend == "native" and ce_head.supported(fc, "mfma")):
+                logging.warning("--head_gemm mfma cannot run here (backend %s, device %s, %d x %d classifier): "
+                                "using the fma path", self.backend, fc.weight.device, fc.in_features,
+                                fc.out_features)
+                want = "fma"
+            self._head_gemm = want
+        return self._head_gemm
 
     def _extra_state(self, epoch):
         return dict(super()._extra_state(epoch), n_cls=int(self.opt.n_cls), label_frac=float(self.opt.label_frac))
@@ -116,7 +131,8 @@ class SupervisedEngine(TrainEngine):
         with ph("forward"):
             feat = self.runner.encode(x)
         with ph("loss"):
-            loss, stats = classifier_ce(feat, self.model.fc, labels, native=self.backend == "native")
+            loss, stats = classifier_ce(feat, self.model.fc, labels, native=self.backend == "native",
+                                        gemm=self.head_gemm())
         self._backward_and_update(loss, zeroed)
         return {"loss_local": loss.detach(), "stats": stats}
 
@@ -190,7 +206,10 @@ class SupervisedEngine(TrainEngine):
         fc = self.model.fc
         native = self.backend == "native"
         encode, restore = linear_probe.eval_encoder(self.model, self.backend, self.runner)   # the weights of NOW
-        native_ce = native and linear_probe.supported(self.model)
+        gemm = self.head_gemm()
+        native_ce = native and linear_probe.supported(self.model, gemm=gemm)
+        step = getattr(_ext.require(), "linear_ce_step_mfma" if gemm == "mfma" else "linear_ce_step") \
+            if native_ce else None
         tot = torch.zeros(3, dtype=torch.float64, device=self.device)
         n, vb = len(self.val), self.opt.val_batch_size
         for s in range(0, n, vb):
@@ -199,8 +218,8 @@ class SupervisedEngine(TrainEngine):
             labels = self.val.labels[idx]
             feat = encode(x)
             if native_ce:
-                st = _ext.require().linear_ce_step(feat.float().contiguous(), fc.weight.data, fc.bias.data,
-                                                   labels.long(), None, None, 0.0, 0.0, 0.0, False, False)[1]
+                st = step(feat.float().contiguous(), fc.weight.data, fc.bias.data,
+                          labels.long(), None, None, 0.0, 0.0, 0.0, False, False)[1]
             else:
                 st = classifier_ce(feat, fc, labels, native=False)[1]
             tot += st.double()

@@ -17,6 +17,11 @@ itself, so its outputs are valid at once.
 
 Unsupported shapes (K ≠ 64·2^j, K > 2048, C > 1024), CPU tensors and the ``torch`` backend use
 ``F.linear`` + ``F.cross_entropy``: the same values through stock torch ops.
+
+``gemm="mfma"`` (``--head_gemm mfma``) runs the three GEMMs of the node on split-bf16 MFMA
+kernels (csrc/kernels/head_gemm.hip) for any K = 64·j <= 4096 and C <= 32768: two launches
+forward, two backward, the same outputs, sinks and statistics convention. The default stays
+``fma``.
 """
 from __future__ import annotations
 
@@ -28,25 +33,29 @@ import torch.nn.functional as F
 from . import _ext, sinks
 
 
-def supported(fc: torch.nn.Linear) -> bool:
-    """Whether the native node can run this classifier (its launchers refuse anything else)."""
+def supported(fc: torch.nn.Linear, gemm: str = "fma") -> bool:
+    """Whether the native node can run this classifier (its launchers refuse anything else).
+    ``gemm="mfma"``: the range of csrc/kernels/head_gemm.hip (K = 64·j <= 4096, C <= 32768)."""
+    from .linear_probe import shape_supported
+    ok = shape_supported(fc.in_features, fc.out_features, gemm) and fc.out_features >= 1
     if not fc.weight.is_cuda or fc.bias is None or fc.weight.dtype != torch.float32 or not _ext.available():
         return False
-    k, c = fc.in_features, fc.out_features
-    return k % 64 == 0 and k <= 2048 and ((k // 64) & (k // 64 - 1)) == 0 and 1 <= c <= 1024
+    return ok
 
 
 class _ClassifierCE(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, feat, labels, fc, record, *params):
+    def forward(ctx, feat, labels, fc, record, gemm, *params):
         m = _ext.require()
+        fwd = m.ce_head_fwd_mfma if gemm == "mfma" else m.ce_head_fwd
         x = feat.detach().float().contiguous()
         w = fc.weight.detach()
         # record: a backward will follow (decided by the caller: grad mode is off in here)
-        need = [ctx.needs_input_grad[0], any(ctx.needs_input_grad[4:])]
-        logits, dz, rowstat, stats, loss = m.ce_head_fwd(x, w, fc.bias.detach(), labels, not record)
+        need = [ctx.needs_input_grad[0], any(ctx.needs_input_grad[5:])]
+        logits, dz, rowstat, stats, loss = fwd(x, w, fc.bias.detach(), labels, not record)
         ctx.save_for_backward(x, dz, w, rowstat, stats, loss)
         ctx.fc = fc
+        ctx.gemm = gemm
         ctx.params = params
         ctx.need = need
         ctx.feat_dtype = feat.dtype
@@ -60,22 +69,28 @@ class _ClassifierCE(torch.autograd.Function):
         need_dx, need_dw = ctx.need
         t = sinks.target
         go = gout.detach().float().contiguous()
-        dx = _ext.require().ce_head_bwd(x, dz, w, go, rowstat, stats, loss,
-                                        t(fc.weight) if need_dw else None, t(fc.bias) if need_dw else None, need_dx)
+        m = _ext.require()
+        bwd = m.ce_head_bwd_mfma if ctx.gemm == "mfma" else m.ce_head_bwd
+        dx = bwd(x, dz, w, go, rowstat, stats, loss,
+                 t(fc.weight) if need_dw else None, t(fc.bias) if need_dw else None, need_dx)
         if need_dw:
             sinks.notify(ctx.params)
-        return (dx.to(ctx.feat_dtype) if dx is not None else None, None, None, None) + (None,) * len(ctx.params)
+        return (dx.to(ctx.feat_dtype) if dx is not None else None, None, None, None, None) + (None,) * len(ctx.params)
 
 
 def classifier_ce_logits(feat: torch.Tensor, fc: torch.nn.Linear, labels: torch.Tensor,
-                         native: bool = True) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+                         native: bool = True, gemm: str = "fma") -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """(loss, stats, logits) of ``F.cross_entropy(fc(feat), labels)``: ``loss`` the batch mean,
     ``stats`` = [Σ_rows CE, top-1 hits, top-5 hits] (fp32, no gradient), ``logits`` [B, C] (no
-    gradient). ``native=False`` forces the torch ops."""
+    gradient). ``native=False`` forces the torch ops. ``gemm="mfma"``: the GEMMs of the node on
+    csrc/kernels/head_gemm.hip; a classifier outside its range is an error here (the engines decide
+    beforehand, with one warning, which path a run takes)."""
     labels = labels.long()
-    if native and feat.is_cuda and supported(fc):
+    if native and feat.is_cuda and gemm == "mfma" and not supported(fc, "mfma"):
+        raise ValueError(f"gemm='mfma' cannot run a {fc.in_features} x {fc.out_features} classifier")
+    if native and feat.is_cuda and supported(fc, gemm):
         record = torch.is_grad_enabled() and (feat.requires_grad or fc.weight.requires_grad or fc.bias.requires_grad)
-        return _ClassifierCE.apply(feat, labels.contiguous(), fc, record, fc.weight, fc.bias)
+        return _ClassifierCE.apply(feat, labels.contiguous(), fc, record, gemm, fc.weight, fc.bias)
     logits = F.linear(feat.float(), fc.weight, fc.bias)
     loss = F.cross_entropy(logits, labels)
     with torch.no_grad():
@@ -87,7 +102,7 @@ def classifier_ce_logits(feat: torch.Tensor, fc: torch.nn.Linear, labels: torch.
 
 
 def classifier_ce(feat: torch.Tensor, fc: torch.nn.Linear, labels: torch.Tensor,
-                  native: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+                  native: bool = True, gemm: str = "fma") -> Tuple[torch.Tensor, torch.Tensor]:
     """``(loss, stats)`` — see :func:`classifier_ce_logits`."""
-    loss, stats, _ = classifier_ce_logits(feat, fc, labels, native)
+    loss, stats, _ = classifier_ce_logits(feat, fc, labels, native, gemm)
     return loss, stats

@@ -113,8 +113,10 @@ class NativeLinearCE:
     """``LinearClassifier`` trained with cross-entropy and SGD on the native path. Holds its
     own momentum buffers (the linear probe writes no checkpoint, main_linear.py)."""
 
-    def __init__(self, classifier: torch.nn.Module, momentum: float = 0.9, weight_decay: float = 0.0):
+    def __init__(self, classifier: torch.nn.Module, momentum: float = 0.9, weight_decay: float = 0.0,
+                 gemm: str = "fma"):
         fc = classifier.fc
+        self.gemm = _check_gemm(gemm)
         self.W, self.b = fc.weight, fc.bias
         self.momentum = float(momentum)
         self.weight_decay = float(weight_decay)
@@ -125,17 +127,20 @@ class NativeLinearCE:
     def train_batch(self, feats: torch.Tensor, labels: torch.Tensor, lr: float):
         """One SGD step on the batch; returns (logits, stats [Σ CE, hits@1, hits@5]) on device."""
         with torch.no_grad():
-            out = _ext.require().linear_ce_step(feats.float().contiguous(), self.W.data, self.b.data, labels.long(),
-                                                self.bufW, self.bufb, float(lr), self.momentum, self.weight_decay,
-                                                self.first, True)
+            out = self._op()(feats.float().contiguous(), self.W.data, self.b.data, labels.long(),
+                             self.bufW, self.bufb, float(lr), self.momentum, self.weight_decay, self.first, True)
         self.first = False
         return out[0], out[1]
 
     @torch.no_grad()
     def eval_batch(self, feats: torch.Tensor, labels: torch.Tensor):
-        out = _ext.require().linear_ce_step(feats.float().contiguous(), self.W.data, self.b.data, labels.long(),
-                                            None, None, 0.0, 0.0, 0.0, False, False)
+        out = self._op()(feats.float().contiguous(), self.W.data, self.b.data, labels.long(),
+                         None, None, 0.0, 0.0, 0.0, False, False)
         return out[0], out[1]
+
+    def _op(self):
+        m = _ext.require()
+        return m.linear_ce_step_mfma if self.gemm == "mfma" else m.linear_ce_step
 
 
 SWEEP_MAX_HEADS = 16
@@ -147,8 +152,10 @@ class NativeLinearSweep:
     (csrc/kernels/linear_ce_sweep.hip). Every head starts from ``classifier``'s weights and is
     bit-identical to a :class:`NativeLinearCE` run alone with its settings."""
 
-    def __init__(self, classifier: torch.nn.Module, weight_decays: Sequence[float], momentum: float = 0.9):
+    def __init__(self, classifier: torch.nn.Module, weight_decays: Sequence[float], momentum: float = 0.9,
+                 gemm: str = "fma"):
         fc = classifier.fc
+        self.gemm = _check_gemm(gemm)
         self.G = len(weight_decays)
         if not 1 <= self.G <= SWEEP_MAX_HEADS:
             raise ValueError(f"a sweep has 1..{SWEEP_MAX_HEADS} heads, got {self.G}")
@@ -163,31 +170,55 @@ class NativeLinearSweep:
     @torch.no_grad()
     def train_batch(self, feats: torch.Tensor, labels: torch.Tensor, lrs: Sequence[float]):
         """One SGD step of every head; returns (logits [G, B, C], stats [G, 3]) on device."""
-        out = _ext.require().linear_ce_sweep_step(feats.float().contiguous(), self.W, self.b, labels.long(),
-                                                  self.bufW, self.bufb, [float(v) for v in lrs], self.momentum,
-                                                  self.weight_decays, self.first, True)
+        out = self._op()(feats.float().contiguous(), self.W, self.b, labels.long(),
+                         self.bufW, self.bufb, [float(v) for v in lrs], self.momentum,
+                         self.weight_decays, self.first, True)
         self.first = False
         return out[0], out[1]
 
     @torch.no_grad()
     def eval_batch(self, feats: torch.Tensor, labels: torch.Tensor):
         zeros = [0.0] * self.G
-        out = _ext.require().linear_ce_sweep_step(feats.float().contiguous(), self.W, self.b, labels.long(),
-                                                  None, None, zeros, 0.0, zeros, False, False)
+        out = self._op()(feats.float().contiguous(), self.W, self.b, labels.long(),
+                         None, None, zeros, 0.0, zeros, False, False)
         return out[0], out[1]
+
+    def _op(self):
+        m = _ext.require()
+        return m.linear_ce_sweep_step_mfma if self.gemm == "mfma" else m.linear_ce_sweep_step
 
     def head_state(self, g: int) -> Dict[str, torch.Tensor]:
         """``LinearClassifier`` state dict of head ``g``."""
         return {"fc.weight": self.W[g].clone(), "fc.bias": self.b[g].clone()}
 
 
-def supported(classifier: torch.nn.Module, feat_dim: Optional[int] = None) -> bool:
-    fc = getattr(classifier, "fc", None)
-    if fc is None or not fc.weight.is_cuda or not _ext.available():
-        return False
-    k, c = fc.in_features, fc.out_features
+GEMMS = ("fma", "mfma")
+
+
+def _check_gemm(gemm: str) -> str:
+    if gemm not in GEMMS:
+        raise ValueError(f"gemm must be one of {GEMMS}, got {gemm!r}")
+    return gemm
+
+
+def shape_supported(k: int, c: int, gemm: str = "fma") -> bool:
+    """The (feature, class) range of the classifier kernels: ``fma`` K = 64·2^j <= 2048 and
+    C <= 1024 (linear_ce.hip), ``mfma`` K = 64·j <= 4096 and C <= 32768 (head_gemm.hip)."""
+    if _check_gemm(gemm) == "mfma":
+        return k % 64 == 0 and 64 <= k <= 4096 and 1 <= c <= 32768
     return k % 64 == 0 and k <= 2048 and ((k // 64) & (k // 64 - 1)) == 0 and c <= 1024
 
 
-def sweep_supported(classifier: torch.nn.Module, G: int) -> bool:
-    return 1 <= G <= SWEEP_MAX_HEADS and supported(classifier)
+def supported(classifier: torch.nn.Module, feat_dim: Optional[int] = None, gemm: str = "fma") -> bool:
+    fc = getattr(classifier, "fc", None)
+    _check_gemm(gemm)
+    if fc is None or not fc.weight.is_cuda or not _ext.available():
+        return False
+    return shape_supported(fc.in_features, fc.out_features, gemm)
+
+
+def sweep_supported(classifier: torch.nn.Module, G: int, gemm: str = "fma") -> bool:
+    if not (1 <= G <= SWEEP_MAX_HEADS and supported(classifier, gemm=gemm)):
+        return False
+    fc = classifier.fc
+    return gemm == "fma" or G * fc.out_features * fc.in_features < 2 ** 31
