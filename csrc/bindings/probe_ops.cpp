@@ -16,16 +16,35 @@ void check_f32(const torch::Tensor& t, std::vector<int64_t> shape, const char* n
               " must be a contiguous fp32 GPU tensor of shape ", shape);
 }
 
+// The row-indexed ops (*_rows): x is a feature bank [N][K] and labels its labels [N]; the batch is
+// the bank rows rows[0..B) (int64, on the bank's device, values in [0, N): device-resident, so
+// the values themselves are not checked here — the kernels clamp the address into the bank and
+// the checked build traps). Returns the batch size: rows' length, or x's without rows.
+int64_t batch_rows(const torch::Tensor& x, const torch::Tensor& labels, const OptT& rows) {
+  TORCH_CHECK(x.dim() == 2, "x [B][K]");
+  const int64_t N = x.size(0);
+  if (!rows.has_value()) return N;
+  TORCH_CHECK(rows->is_cuda() && rows->scalar_type() == at::kLong && rows->dim() == 1 && rows->is_contiguous() &&
+                  rows->get_device() == x.get_device(),
+              "rows: contiguous int64 [B] on the bank's device");
+  TORCH_CHECK(N >= 1 && labels.numel() == N && labels.is_cuda() && labels.get_device() == x.get_device(),
+              "rows: a bank x [N][K] with labels [N] on its device, N >= 1");
+  return rows->numel();
+}
+
+const int64_t* rows_ptr(const OptT& rows) { return rows.has_value() ? rows->data_ptr<int64_t>() : nullptr; }
+
 // the shape / dtype checks shared by linear_ce_step and the ce_head ops
 void check_classifier(const torch::Tensor& x, const torch::Tensor& W, const torch::Tensor& b,
-                      const torch::Tensor& labels) {
+                      const torch::Tensor& labels, const OptT& rows = c10::nullopt) {
   TORCH_CHECK(x.dim() == 2 && W.dim() == 2, "x [B][K], W [C][K]");
-  const int64_t B = x.size(0), K = x.size(1), C = W.size(0);
-  check_f32(x, {B, K}, "x");
+  const int64_t N = x.size(0), K = x.size(1), C = W.size(0);
+  check_f32(x, {N, K}, "x");
   check_f32(W, {C, K}, "W");
   check_f32(b, {C}, "b");
-  TORCH_CHECK(labels.is_cuda() && labels.scalar_type() == at::kLong && labels.numel() == B && labels.is_contiguous(),
-              "labels: int64 [B]");
+  TORCH_CHECK(labels.is_cuda() && labels.scalar_type() == at::kLong && labels.numel() == N && labels.is_contiguous(),
+              rows.has_value() ? "labels: int64 [N], one per bank row" : "labels: int64 [B]");
+  const int64_t B = batch_rows(x, labels, rows);
   TORCH_CHECK(B >= 1 && linear_ce_supported((int)K, (int)C) && ((K / 64) & (K / 64 - 1)) == 0,
               "linear_ce: K = 64·2^j <= 2048, C <= 1024");
   TORCH_CHECK(B * C < (1LL << 31) && B * K < (1LL << 31), "linear_ce: sizes");
@@ -34,11 +53,11 @@ void check_classifier(const torch::Tensor& x, const torch::Tensor& W, const torc
 // One classifier batch. train: logits, the mean-CE gradient and the SGD update of (W, b)
 // with momentum buffers (bufW, bufb; `first` = no momentum history yet); eval: logits only.
 // Returns [logits [B][C], stats [3] = (Σ_rows CE, top-1 hits, top-5 hits)].
-std::vector<torch::Tensor> linear_ce_step(torch::Tensor x, torch::Tensor W, torch::Tensor b, torch::Tensor labels,
-                                          OptT bufW, OptT bufb, double lr, double momentum, double wd, bool first,
-                                          bool train) {
-  check_classifier(x, W, b, labels);
-  const int64_t B = x.size(0), K = x.size(1), C = W.size(0);
+std::vector<torch::Tensor> linear_ce_step_impl(torch::Tensor x, torch::Tensor W, torch::Tensor b,
+                                               torch::Tensor labels, OptT rows, OptT bufW, OptT bufb, double lr,
+                                               double momentum, double wd, bool first, bool train) {
+  check_classifier(x, W, b, labels, rows);
+  const int64_t B = batch_rows(x, labels, rows), N = x.size(0), K = x.size(1), C = W.size(0);
   if (train) {
     TORCH_CHECK(bufW.has_value() && bufb.has_value(), "momentum buffers required for a training step");
     check_f32(*bufW, {C, K}, "bufW");
@@ -54,15 +73,28 @@ std::vector<torch::Tensor> linear_ce_step(torch::Tensor x, torch::Tensor W, torc
   check_hip(launch_linear_ce_fwd(x.data_ptr<float>(), W.data_ptr<float>(), b.data_ptr<float>(),
                                  labels.data_ptr<int64_t>(), (int)B, (int)K, (int)C, (float)(1.0 / B),
                                  logits.data_ptr<float>(), train ? dz.data_ptr<float>() : nullptr,
-                                 rowstat.data_ptr<float>(), cur_stream()),
+                                 rowstat.data_ptr<float>(), cur_stream(), rows_ptr(rows), (long)N),
             "linear_ce_fwd");
   check_hip(launch_linear_ce_sgd(x.data_ptr<float>(), train ? dz.data_ptr<float>() : nullptr, (int)B, (int)K, (int)C,
                                  train ? W.data_ptr<float>() : nullptr, train ? b.data_ptr<float>() : nullptr,
                                  train ? bufW->data_ptr<float>() : nullptr, train ? bufb->data_ptr<float>() : nullptr,
                                  (float)lr, (float)momentum, (float)wd, first ? 1 : 0, rowstat.data_ptr<float>(),
-                                 stats.data_ptr<float>(), cur_stream()),
+                                 stats.data_ptr<float>(), cur_stream(), rows_ptr(rows), (long)N),
             "linear_ce_sgd");
   return {logits, stats};
+}
+
+std::vector<torch::Tensor> linear_ce_step(torch::Tensor x, torch::Tensor W, torch::Tensor b, torch::Tensor labels,
+                                          OptT bufW, OptT bufb, double lr, double momentum, double wd, bool first,
+                                          bool train) {
+  return linear_ce_step_impl(x, W, b, labels, c10::nullopt, bufW, bufb, lr, momentum, wd, first, train);
+}
+
+// linear_ce_step on the bank rows `rows`: bit-identical to linear_ce_step(x[rows], ..., labels[rows], ...)
+std::vector<torch::Tensor> linear_ce_step_rows(torch::Tensor x, torch::Tensor W, torch::Tensor b,
+                                               torch::Tensor labels, torch::Tensor rows, OptT bufW, OptT bufb,
+                                               double lr, double momentum, double wd, bool first, bool train) {
+  return linear_ce_step_impl(x, W, b, labels, rows, bufW, bufb, lr, momentum, wd, first, train);
 }
 
 // Test-only: linear_ce_step's second launch alone, on a caller-supplied dz [B][C] and rowstat
@@ -103,24 +135,27 @@ torch::Tensor linear_ce_sgd_raw(torch::Tensor x, torch::Tensor dz, torch::Tensor
 // train: bufW [G][C][K], bufb [G][C]; eval: no buffers. Views of larger tensors are allowed when
 // contiguous and 16-byte aligned. Everything is checked before anything is allocated or launched.
 // Returns [logits [G][B][C], stats [G][3]]; head g is bit-identical to linear_ce_step alone.
-std::vector<torch::Tensor> linear_ce_sweep_step(torch::Tensor x, torch::Tensor W, torch::Tensor b,
-                                                torch::Tensor labels, OptT bufW, OptT bufb, std::vector<double> lrs,
-                                                double momentum, std::vector<double> wds, bool first, bool train) {
+std::vector<torch::Tensor> linear_ce_sweep_step_impl(torch::Tensor x, torch::Tensor W, torch::Tensor b,
+                                                     torch::Tensor labels, OptT rows, OptT bufW, OptT bufb,
+                                                     const std::vector<double>& lrs, double momentum,
+                                                     const std::vector<double>& wds, bool first, bool train) {
   TORCH_CHECK(x.dim() == 2 && W.dim() == 3, "x [B][K], W [G][C][K]");
-  const int64_t B = x.size(0), K = x.size(1), G = W.size(0), C = W.size(1);
+  const int64_t N = x.size(0), K = x.size(1), G = W.size(0), C = W.size(1);
   TORCH_CHECK(G >= 1 && G <= kLinearSweepMaxHeads, "linear_ce_sweep: 1 <= G <= ", kLinearSweepMaxHeads, ", got ", G);
   TORCH_CHECK((int64_t)lrs.size() == G && (int64_t)wds.size() == G, "linear_ce_sweep: ", G, " heads need ", G,
               " learning rates and weight decays, got ", lrs.size(), " and ", wds.size());
-  check_f32(x, {B, K}, "x");
+  check_f32(x, {N, K}, "x");
   check_f32(W, {G, C, K}, "W");
   check_f32(b, {G, C}, "b");
-  TORCH_CHECK(labels.is_cuda() && labels.scalar_type() == at::kLong && labels.numel() == B && labels.is_contiguous(),
-              "labels: int64 [B]");
+  TORCH_CHECK(labels.is_cuda() && labels.scalar_type() == at::kLong && labels.numel() == N && labels.is_contiguous(),
+              rows.has_value() ? "labels: int64 [N], one per bank row" : "labels: int64 [B]");
+  const int64_t B = batch_rows(x, labels, rows);
   TORCH_CHECK(B >= 1 && linear_ce_sweep_supported((int)G, (int)K, (int)C),
               "linear_ce_sweep: K = 64·2^j <= 2048, 1 <= C <= 1024, B >= 1");
   TORCH_CHECK(G * B * C < (1LL << 31) && B * K < (1LL << 31) && G * C * K < (1LL << 31), "linear_ce_sweep: sizes");
   auto aligned = [](const torch::Tensor& t) { return reinterpret_cast<uintptr_t>(t.data_ptr<float>()) % 16 == 0; };
-  TORCH_CHECK(aligned(x) && aligned(W), "linear_ce_sweep: x and W must be 16-byte aligned");
+  // (a bank is read in place at any 4-byte alignment)
+  TORCH_CHECK((rows.has_value() || aligned(x)) && aligned(W), "linear_ce_sweep: x and W must be 16-byte aligned");
   const int dev = x.get_device();
   TORCH_CHECK(W.get_device() == dev && b.get_device() == dev && labels.get_device() == dev,
               "linear_ce_sweep: one device");
@@ -146,7 +181,7 @@ std::vector<torch::Tensor> linear_ce_sweep_step(torch::Tensor x, torch::Tensor W
   check_hip(launch_linear_ce_sweep_fwd(x.data_ptr<float>(), W.data_ptr<float>(), b.data_ptr<float>(),
                                        labels.data_ptr<int64_t>(), (int)G, (int)B, (int)K, (int)C, (float)(1.0 / B),
                                        logits.data_ptr<float>(), train ? dz.data_ptr<float>() : nullptr,
-                                       rowstat.data_ptr<float>(), cur_stream()),
+                                       rowstat.data_ptr<float>(), cur_stream(), rows_ptr(rows), (long)N),
             "linear_ce_sweep_fwd");
   check_hip(launch_linear_ce_sweep_sgd(x.data_ptr<float>(), train ? dz.data_ptr<float>() : nullptr, (int)G, (int)B,
                                        (int)K, (int)C, train ? W.data_ptr<float>() : nullptr,
@@ -154,9 +189,23 @@ std::vector<torch::Tensor> linear_ce_sweep_step(torch::Tensor x, torch::Tensor W
                                        train ? bufW->data_ptr<float>() : nullptr,
                                        train ? bufb->data_ptr<float>() : nullptr, lr, wd, (float)momentum,
                                        first ? 1 : 0, rowstat.data_ptr<float>(), stats.data_ptr<float>(),
-                                       cur_stream()),
+                                       cur_stream(), rows_ptr(rows), (long)N),
             "linear_ce_sweep_sgd");
   return {logits, stats};
+}
+
+std::vector<torch::Tensor> linear_ce_sweep_step(torch::Tensor x, torch::Tensor W, torch::Tensor b,
+                                                torch::Tensor labels, OptT bufW, OptT bufb, std::vector<double> lrs,
+                                                double momentum, std::vector<double> wds, bool first, bool train) {
+  return linear_ce_sweep_step_impl(x, W, b, labels, c10::nullopt, bufW, bufb, lrs, momentum, wds, first, train);
+}
+
+// linear_ce_sweep_step on the bank rows `rows`: bit-identical to the plain op on x[rows], labels[rows]
+std::vector<torch::Tensor> linear_ce_sweep_step_rows(torch::Tensor x, torch::Tensor W, torch::Tensor b,
+                                                     torch::Tensor labels, torch::Tensor rows, OptT bufW, OptT bufb,
+                                                     std::vector<double> lrs, double momentum,
+                                                     std::vector<double> wds, bool first, bool train) {
+  return linear_ce_sweep_step_impl(x, W, b, labels, rows, bufW, bufb, lrs, momentum, wds, first, train);
 }
 
 // Training form, forward: [logits [B][C], dz [B][C] = (softmax − onehot) / B, rowstat [B][3],
@@ -230,33 +279,35 @@ c10::optional<torch::Tensor> ce_head_bwd(torch::Tensor x, torch::Tensor dz, torc
 
 bool aligned16(const torch::Tensor& t) { return reinterpret_cast<uintptr_t>(t.data_ptr<float>()) % 16 == 0; }
 
-void check_labels(const torch::Tensor& labels, int64_t B, int dev) {
+void check_labels(const torch::Tensor& labels, int64_t B, int dev, bool bank = false) {
   TORCH_CHECK(labels.is_cuda() && labels.scalar_type() == at::kLong && labels.numel() == B && labels.is_contiguous() &&
                   labels.get_device() == dev,
-              "labels: int64 [B] on x's device");
+              bank ? "labels: int64 [N], one per bank row, on the bank's device" : "labels: int64 [B] on x's device");
 }
 
 // W [G][C][K] or its single-head [C][K] form (heads = false); everything checked before any
 // allocation or launch
 std::vector<torch::Tensor> head_gemm_step(const char* op, bool heads, torch::Tensor x, torch::Tensor W,
-                                          torch::Tensor b, torch::Tensor labels, OptT bufW, OptT bufb,
+                                          torch::Tensor b, torch::Tensor labels, OptT rows, OptT bufW, OptT bufb,
                                           const std::vector<double>& lrs, double momentum,
                                           const std::vector<double>& wds, bool first, bool train) {
   TORCH_CHECK(x.dim() == 2 && W.dim() == (heads ? 3 : 2), op, ": x [B][K], W ", heads ? "[G][C][K]" : "[C][K]");
-  const int64_t B = x.size(0), K = x.size(1), G = heads ? W.size(0) : 1, C = W.size(heads ? 1 : 0);
+  const int64_t N = x.size(0), K = x.size(1), G = heads ? W.size(0) : 1, C = W.size(heads ? 1 : 0);
   TORCH_CHECK(G >= 1 && G <= kLinearSweepMaxHeads, op, ": 1 <= G <= ", kLinearSweepMaxHeads, ", got ", G);
   TORCH_CHECK((int64_t)lrs.size() == G && (int64_t)wds.size() == G, op, ": ", G, " heads need ", G,
               " learning rates and weight decays, got ", lrs.size(), " and ", wds.size());
   const std::vector<int64_t> wshape = heads ? std::vector<int64_t>{G, C, K} : std::vector<int64_t>{C, K};
   const std::vector<int64_t> bshape = heads ? std::vector<int64_t>{G, C} : std::vector<int64_t>{C};
-  check_f32(x, {B, K}, "x");
+  check_f32(x, {N, K}, "x");
   check_f32(W, wshape, "W");
   check_f32(b, bshape, "b");
   const int dev = x.get_device();
-  check_labels(labels, B, dev);
+  check_labels(labels, N, dev, rows.has_value());
+  const int64_t B = batch_rows(x, labels, rows);
   TORCH_CHECK(B >= 1 && B < (1LL << 31) && head_gemm_supported((int)G, (int)B, (int)K, (int)C), op,
               ": K % 64 == 0, 64 <= K <= 4096, 1 <= C <= 32768, B >= 1, element counts below 2^31");
-  TORCH_CHECK(aligned16(x) && aligned16(W), op, ": x and W must be 16-byte aligned");
+  // (a bank is read in place at any 4-byte alignment)
+  TORCH_CHECK((rows.has_value() || aligned16(x)) && aligned16(W), op, ": x and W must be 16-byte aligned");
   TORCH_CHECK(W.get_device() == dev && b.get_device() == dev, op, ": one device");
   if (train) {
     TORCH_CHECK(bufW.has_value() && bufb.has_value(), "momentum buffers required for a training step");
@@ -280,13 +331,14 @@ std::vector<torch::Tensor> head_gemm_step(const char* op, bool heads, torch::Ten
   check_hip(launch_head_gemm_logits(x.data_ptr<float>(), W.data_ptr<float>(), b.data_ptr<float>(),
                                     labels.data_ptr<int64_t>(), (int)G, (int)B, (int)K, (int)C, (float)(1.0 / B),
                                     logits.data_ptr<float>(), train ? dz.data_ptr<float>() : nullptr,
-                                    rowstat.data_ptr<float>(), cur_stream()),
+                                    rowstat.data_ptr<float>(), cur_stream(), rows_ptr(rows), (long)N),
             op);
   if (train)
     check_hip(launch_head_gemm_sgd(x.data_ptr<float>(), dz.data_ptr<float>(), (int)G, (int)B, (int)K, (int)C,
                                    W.data_ptr<float>(), b.data_ptr<float>(), bufW->data_ptr<float>(),
                                    bufb->data_ptr<float>(), lr, wd, (float)momentum, first ? 1 : 0,
-                                   rowstat.data_ptr<float>(), stats.data_ptr<float>(), cur_stream()),
+                                   rowstat.data_ptr<float>(), stats.data_ptr<float>(), cur_stream(), rows_ptr(rows),
+                                   (long)N),
               op);
   else
     check_hip(launch_head_gemm_stats((int)G, (int)B, (int)K, (int)C, rowstat.data_ptr<float>(),
@@ -298,16 +350,31 @@ std::vector<torch::Tensor> head_gemm_step(const char* op, bool heads, torch::Ten
 std::vector<torch::Tensor> linear_ce_step_mfma(torch::Tensor x, torch::Tensor W, torch::Tensor b,
                                                torch::Tensor labels, OptT bufW, OptT bufb, double lr, double momentum,
                                                double wd, bool first, bool train) {
-  return head_gemm_step("linear_ce_step_mfma", false, x, W, b, labels, bufW, bufb, {lr}, momentum, {wd}, first,
-                        train);
+  return head_gemm_step("linear_ce_step_mfma", false, x, W, b, labels, c10::nullopt, bufW, bufb, {lr}, momentum, {wd},
+                        first, train);
+}
+
+std::vector<torch::Tensor> linear_ce_step_mfma_rows(torch::Tensor x, torch::Tensor W, torch::Tensor b,
+                                                    torch::Tensor labels, torch::Tensor rows, OptT bufW, OptT bufb,
+                                                    double lr, double momentum, double wd, bool first, bool train) {
+  return head_gemm_step("linear_ce_step_mfma_rows", false, x, W, b, labels, rows, bufW, bufb, {lr}, momentum, {wd},
+                        first, train);
 }
 
 std::vector<torch::Tensor> linear_ce_sweep_step_mfma(torch::Tensor x, torch::Tensor W, torch::Tensor b,
                                                      torch::Tensor labels, OptT bufW, OptT bufb,
                                                      std::vector<double> lrs, double momentum, std::vector<double> wds,
                                                      bool first, bool train) {
-  return head_gemm_step("linear_ce_sweep_step_mfma", true, x, W, b, labels, bufW, bufb, lrs, momentum, wds, first,
-                        train);
+  return head_gemm_step("linear_ce_sweep_step_mfma", true, x, W, b, labels, c10::nullopt, bufW, bufb, lrs, momentum,
+                        wds, first, train);
+}
+
+std::vector<torch::Tensor> linear_ce_sweep_step_mfma_rows(torch::Tensor x, torch::Tensor W, torch::Tensor b,
+                                                          torch::Tensor labels, torch::Tensor rows, OptT bufW,
+                                                          OptT bufb, std::vector<double> lrs, double momentum,
+                                                          std::vector<double> wds, bool first, bool train) {
+  return head_gemm_step("linear_ce_sweep_step_mfma_rows", true, x, W, b, labels, rows, bufW, bufb, lrs, momentum, wds,
+                        first, train);
 }
 
 void check_head_gemm_classifier(const char* op, const torch::Tensor& x, const torch::Tensor& W) {
@@ -386,6 +453,18 @@ c10::optional<torch::Tensor> ce_head_bwd_mfma(torch::Tensor x, torch::Tensor dz,
 }  // namespace
 
 void register_probe(pybind11::module& m) {
+  // the row-indexed steps: x a feature bank [N][K], labels [N], the batch = bank rows `rows` (int64 [B],
+  // on the device, in [0, N)), read in place; otherwise the argument lists of their plain siblings
+  const char* rows_doc = "on bank rows `rows`: bit-identical to the plain op on x[rows], labels[rows]";
+#define SDX_ROWS_OP(name, lr_arg, wd_arg)                                                                         \
+  m.def(#name, &name, rows_doc, pybind11::arg("x"), pybind11::arg("W"), pybind11::arg("b"), pybind11::arg("labels"), \
+        pybind11::arg("rows"), pybind11::arg("bufW"), pybind11::arg("bufb"), pybind11::arg(lr_arg),               \
+        pybind11::arg("momentum"), pybind11::arg(wd_arg), pybind11::arg("first"), pybind11::arg("train"))
+  SDX_ROWS_OP(linear_ce_step_rows, "lr", "wd");
+  SDX_ROWS_OP(linear_ce_sweep_step_rows, "lrs", "wds");
+  SDX_ROWS_OP(linear_ce_step_mfma_rows, "lr", "wd");
+  SDX_ROWS_OP(linear_ce_sweep_step_mfma_rows, "lrs", "wds");
+#undef SDX_ROWS_OP
   m.def("linear_ce_step_mfma", &linear_ce_step_mfma,
         "linear_ce_step on bf16x3 MFMA GEMMs (head_gemm.hip): K = 64·j <= 4096, C <= 32768",
         pybind11::arg("x"), pybind11::arg("W"), pybind11::arg("b"), pybind11::arg("labels"), pybind11::arg("bufW"),

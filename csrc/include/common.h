@@ -133,6 +133,34 @@ __device__ __forceinline__ uint32_t fdiv(uint32_t x, const FastDiv& f) {
   return (__umulhi(x, f.mul) + x) >> f.shr;
 }
 
+// Row-indexed classifier step (linear_ce.hip, linear_ce_sweep.hip, head_gemm.hip): batch row b is
+// row rows[b] of a feature bank of N rows. rows[b] must lie in [0, N); the index is clamped into
+// the bank all the same, so no read leaves it, and the checked build traps on a stray one.
+__device__ __forceinline__ size_t bank_row(const int64_t* __restrict__ rows, int b, long N) {
+  const int64_t r = rows[b];
+  SDX_DCHECK(r >= 0 && r < N);
+  return (size_t)(r < 0 ? 0 : (r >= N ? N - 1 : r));
+}
+
+enum RowMode {
+  kRowsNone = 0,    // x [B][K] is the batch itself
+  kRowsVec = 1,     // x is the bank, its rows 16-byte aligned
+  kRowsScalar = 2,  // x is the bank at any 4-byte alignment
+};
+
+// x[b][k..k+3] of the batch, or of bank row rows[b]
+template <int RM>
+__device__ __forceinline__ float4 load_x4(const float* __restrict__ x, const int64_t* __restrict__ rows, long N,
+                                          int b, int K, int k) {
+  if constexpr (RM == kRowsNone) {
+    return *reinterpret_cast<const float4*>(x + (size_t)b * K + k);
+  } else {
+    const float* src = x + bank_row(rows, b, N) * K + k;
+    if constexpr (RM == kRowsVec) return *reinterpret_cast<const float4*>(src);
+    return make_float4(src[0], src[1], src[2], src[3]);
+  }
+}
+
 }  // namespace sdx
 
 #ifndef SDX_NT_EW

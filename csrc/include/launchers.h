@@ -21,13 +21,19 @@ hipError_t launch_norm_stats(const float* x, int N, int D, int mode, double* sum
 // ---- linear classifier + cross-entropy (linear_ce.hip) -------------------------
 // K = 64·2^j <= 2048, C <= 1024; every launcher returns hipErrorInvalidValue outside that range
 bool linear_ce_supported(int K, int C);
+// The row-indexed form of the probe launchers here and below (rows != nullptr): x is a feature
+// bank [N][K] and labels its labels [N]; batch row b is bank row rows[b] (B device-resident int64
+// values in [0, N)), read in place — same launches, no gathered copy, bit-identical to the plain
+// form on x[rows], labels[rows]. The bank needs 4-byte alignment only (16 bytes: wider loads).
 // logits [B][C], dz = (softmax − onehot)·gscale (optional), rowstat [B][3] = (CE, hit@1, hit@5)
 hipError_t launch_linear_ce_fwd(const float* x, const float* W, const float* bias, const int64_t* labels, int B,
-                                int K, int C, float gscale, float* logits, float* dz, float* rowstat, hipStream_t s);
+                                int K, int C, float gscale, float* logits, float* dz, float* rowstat, hipStream_t s,
+                                const int64_t* rows = nullptr, long N = 0);
 // probe form: gradient + SGD update of (W, b) in place, stats[3] = Σ_rows rowstat
 hipError_t launch_linear_ce_sgd(const float* x, const float* dz, int B, int K, int C, float* W, float* bias,
                                 float* bufW, float* bufb, float lr, float mom, float wd, int first,
-                                const float* rowstat, float* stats, hipStream_t s);
+                                const float* rowstat, float* stats, hipStream_t s, const int64_t* rows = nullptr,
+                                long N = 0);
 // training form: dX = gout·dz·W (optional), dW += gout·dzᵀ·x and db += gout·Σ_b dz (optional,
 // both or neither; 16-byte aligned), stats[3] = Σ_rows rowstat, loss = stats[0] / B.
 // gout: the upstream scalar gradient in device memory
@@ -46,14 +52,15 @@ bool head_gemm_supported(int G, int B, int K, int C);
 // (optional), rowstat
 hipError_t launch_head_gemm_logits(const float* x, const float* W, const float* bias, const int64_t* labels, int G,
                                    int B, int K, int C, float gscale, float* logits, float* dz, float* rowstat,
-                                   hipStream_t s);
+                                   hipStream_t s, const int64_t* rows = nullptr, long N = 0);
 // 1 launch: stats [G][3] = Σ_rows rowstat (fp64, row order); loss (optional, G = 1) = stats[0] / B
 hipError_t launch_head_gemm_stats(int G, int B, int K, int C, const float* rowstat, float* stats, float* loss,
                                   hipStream_t s);
 // 1 launch: weight gradients + in-place SGD of every head (lrs / wds: G host values), biases and stats
 hipError_t launch_head_gemm_sgd(const float* x, const float* dz, int G, int B, int K, int C, float* W, float* bias,
                                 float* bufW, float* bufb, const float* lrs, const float* wds, float mom, int first,
-                                const float* rowstat, float* stats, hipStream_t s);
+                                const float* rowstat, float* stats, hipStream_t s, const int64_t* rows = nullptr,
+                                long N = 0);
 // <= 2 launches: dX = gout·dz·W (optional), dW += gout·dzᵀ·x and db += gout·Σ_b dz (optional, both or
 // neither, at least one of dX / dW), stats, loss
 hipError_t launch_head_gemm_bwd(const float* x, const float* dz, const float* W, int B, int K, int C,
@@ -69,11 +76,12 @@ constexpr int kLinearSweepMaxHeads = 16;
 bool linear_ce_sweep_supported(int G, int K, int C);
 hipError_t launch_linear_ce_sweep_fwd(const float* x, const float* W, const float* bias, const int64_t* labels, int G,
                                       int B, int K, int C, float gscale, float* logits, float* dz, float* rowstat,
-                                      hipStream_t s);
+                                      hipStream_t s, const int64_t* rows = nullptr, long N = 0);
 // lrs / wds: G host values (passed to the kernel by value); W == nullptr: statistics only
 hipError_t launch_linear_ce_sweep_sgd(const float* x, const float* dz, int G, int B, int K, int C, float* W,
                                       float* bias, float* bufW, float* bufb, const float* lrs, const float* wds,
-                                      float mom, int first, const float* rowstat, float* stats, hipStream_t s);
+                                      float mom, int first, const float* rowstat, float* stats, hipStream_t s,
+                                      const int64_t* rows = nullptr, long N = 0);
 
 // ---- fused SupCon / NT-Xent loss (supcon.hip) ---------------------------------
 int supcon_num_splits(int n_own, int n_other);

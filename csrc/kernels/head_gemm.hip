@@ -27,6 +27,12 @@
 //               hit@1, hit@5) with the rank rule #{z_c > z_label} < k; NaN loss and no hits for
 //               a label out of range.
 //   head_stats  the statistics role alone (evaluation, a forward that no backward follows).
+//   row map     the row-indexed probe / sweep step (RowMap, launchers' `rows`): x is a feature bank
+//               and batch row b its row rows[b]. The NT launch indirects the A operand's output
+//               index when the stager fixes its row bases, the TN launch the kTrans operand's
+//               reduction index (8 wave-uniform index reads per slot in front of the 8 dword
+//               loads), ce_rows reads labels[rows[b]]. Same tiles, chunks and sums: bit-identical
+//               to the plain step on x[rows], labels[rows]; no launch and no copy is added.
 //
 // Launches: training step NT + ce_rows + TN = 3 for any G; evaluation NT + ce_rows + head_stats
 // = 3; CE head forward NT + ce_rows = 2 (+ head_stats when no backward follows), backward
@@ -59,6 +65,12 @@ enum LoadMode {
   kTrans = 2,      // output index contiguous, reduction strided: 8 dword loads, lanes along the rows
 };
 enum Epilogue { kLogits = 0, kDx = 1, kDw = 2, kSgd = 3 };
+// the row-indexed step: x is a feature bank and batch row b is its row rows[b]
+enum RowMapUse {
+  kMapNone = 0,
+  kMapOut = 1,   // the operand's output index goes through the map (x as A of the NT logits GEMM)
+  kMapRed = 2,   // its reduction index does (x as the kTrans operand of the TN weight-gradient GEMM)
+};
 
 // element (i, r) — i the output index of this operand, r the reduction index — lives at
 // p[(i / hc)·hs + (i % hc)·si + r·sr]; hc = INT_MAX: no heads
@@ -66,6 +78,13 @@ struct Operand {
   const float* p;
   int lim_i, lim_r, hc;
   long hs, si, sr;
+};
+
+// batch row -> bank row (common.h bank_row). Every head_gemm_kernel / ce_rows_kernel instantiation
+// takes it as its last / third argument; the plain ones ({nullptr, 0}) never read it
+struct RowMap {
+  const int64_t* rows;
+  long n;   // bank rows
 };
 
 struct HeadHyper {
@@ -109,14 +128,16 @@ __device__ __forceinline__ void commit8(const float (&xs)[8], unsigned char* hi_
 }
 
 // A thread stages two (row, 8-element chunk) slots of a 64 x 64 operand tile per step.
-template <int MODE>
+template <int MODE, int MAP = kMapNone>
 struct Stager {
   const float* base[2];   // clamped row base
   bool ok[2];
   int off[2];             // LDS byte offset of the slot
   int rch[2];             // first reduction element of the slot inside the chunk
 
-  __device__ __forceinline__ void init(const Operand& o, int i0, int tid) {
+  __device__ __forceinline__ void init(const Operand& o, const RowMap& rm, int i0, int tid) {
+    static_assert(MAP == kMapNone || (MAP == kMapOut && MODE != kTrans) || (MAP == kMapRed && MODE == kTrans),
+                  "x is staged along its rows (NT) or transposed (TN)");
 #pragma unroll
     for (int ps = 0; ps < 2; ++ps) {
       const int row = MODE == kTrans ? (tid & 63) : ps * 32 + (tid >> 3);
@@ -124,17 +145,34 @@ struct Stager {
       const int i = i0 + row;
       ok[ps] = i < o.lim_i;
       const int ic = ok[ps] ? i : o.lim_i - 1;
-      const int hd = ic / o.hc;
-      base[ps] = o.p + (size_t)hd * o.hs + (size_t)(ic - hd * o.hc) * o.si;
+      if constexpr (MAP == kMapOut) {
+        // (x has no heads) the clamped batch row's bank row: out-of-tile rows still load, then zero
+        base[ps] = o.p + bank_row(rm.rows, ic, rm.n) * o.si;
+      } else {
+        const int hd = ic / o.hc;
+        base[ps] = o.p + (size_t)hd * o.hs + (size_t)(ic - hd * o.hc) * o.si;
+      }
       off[ps] = sw_off(row, chunk);
       rch[ps] = chunk * 8;
     }
   }
 
-  __device__ __forceinline__ void load(const Operand& o, int r0, float (&v)[2][8]) const {
+  __device__ __forceinline__ void load(const Operand& o, const RowMap& rm, int r0, float (&v)[2][8]) const {
 #pragma unroll
     for (int ps = 0; ps < 2; ++ps) {
-      if constexpr (MODE == kVec) {
+      if constexpr (MAP == kMapRed) {
+        // a wave stages one 8-step chunk of the slot (chunk = wave + 4·ps), so the 8 batch rows
+        // and their bank rows are wave-uniform: scalar index loads, then the 8 dword loads
+        const int rb = __builtin_amdgcn_readfirstlane(r0 + rch[ps]);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const int r = rb + j;
+          const bool rok = r < o.lim_r;
+          const int rc = rok ? r : o.lim_r - 1;
+          const float x = base[ps][bank_row(rm.rows, rc, rm.n) * (size_t)o.sr];
+          v[ps][j] = (ok[ps] && rok) ? x : 0.f;
+        }
+      } else if constexpr (MODE == kVec) {
         // lim_r is a multiple of the chunk: no reduction tail on this path
         const float4* s = reinterpret_cast<const float4*>(base[ps] + r0 + rch[ps]);
         const float4 v0 = s[0], v1 = s[1];
@@ -187,8 +225,10 @@ __device__ __forceinline__ void role_block(const GemmParams& p, int role, int n_
   }
 }
 
-template <int LA, int LB, int EPI>
-__global__ __launch_bounds__(256) void head_gemm_kernel(GemmParams p) {
+// MAPA / MAPB: x read from the bank through rm, as the A operand by output index (NT) or the B
+// operand by reduction index (TN); tiles, chunk order and every sum are the same either way
+template <int LA, int LB, int EPI, int MAPA = kMapNone, int MAPB = kMapNone>
+__global__ __launch_bounds__(256) void head_gemm_kernel(GemmParams p, RowMap rm) {
   __shared__ __attribute__((aligned(16))) unsigned char stage[4 * IMG_B];   // a hi, a lo, b hi, b lo
   const int bid = blockIdx.x;
   if constexpr (EPI == kDw || EPI == kSgd) {
@@ -210,13 +250,13 @@ __global__ __launch_bounds__(256) void head_gemm_kernel(GemmParams p) {
   const int tm = bid / p.tiles_n, tn = bid - tm * p.tiles_n;
   const int m0 = tm * T, n0 = tn * T;
 
-  Stager<LA> sa;
-  Stager<LB> sb;
-  sa.init(p.a, m0, tid);
-  sb.init(p.b, n0, tid);
+  Stager<LA, MAPA> sa;
+  Stager<LB, MAPB> sb;
+  sa.init(p.a, rm, m0, tid);
+  sb.init(p.b, rm, n0, tid);
   float va[2][8], vb[2][8];
-  sa.load(p.a, 0, va);
-  sb.load(p.b, 0, vb);
+  sa.load(p.a, rm, 0, va);
+  sb.load(p.b, rm, 0, vb);
 
   f32x4 acc[4];
 #pragma unroll
@@ -230,8 +270,8 @@ __global__ __launch_bounds__(256) void head_gemm_kernel(GemmParams p) {
     }
     __syncthreads();
     if (kc + 1 < p.chunks) {   // the next chunk's loads fly under this chunk's MFMAs
-      sa.load(p.a, (kc + 1) * KC, va);
-      sb.load(p.b, (kc + 1) * KC, vb);
+      sa.load(p.a, rm, (kc + 1) * KC, va);
+      sb.load(p.b, rm, (kc + 1) * KC, vb);
     }
     // acc[t][r] = Σ_k a[m0 + 16t + 4h + r][k] · b[n0 + 16wv + c][k]
 #pragma unroll
@@ -295,16 +335,18 @@ __global__ __launch_bounds__(256) void head_gemm_kernel(GemmParams p) {
 
 __global__ __launch_bounds__(256) void head_stats_kernel(GemmParams p) { role_block<kLogits>(p, 0, 1); }
 
-// rows = G·B logits rows of C classes; labels [B] shared by the heads
+// rows = G·B logits rows of C classes; labels [B] shared by the heads, or (MAPPED) the bank's
+// labels [rm.n] read at rm.rows[b]
+template <bool MAPPED>
 __global__ __launch_bounds__(256) void ce_rows_kernel(const float* __restrict__ logits,
-                                                      const int64_t* __restrict__ labels, int rows, int B, int C,
-                                                      float gscale, float* __restrict__ dz,
+                                                      const int64_t* __restrict__ labels, RowMap rm, int rows, int B,
+                                                      int C, float gscale, float* __restrict__ dz,
                                                       float* __restrict__ rowstat) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * hg::kRowsPerBlock + (threadIdx.x >> 6);
   if (row >= rows) return;
   const float* z = logits + (size_t)row * C;
-  const int64_t lab64 = labels[row % B];
+  const int64_t lab64 = labels[MAPPED ? bank_row(rm.rows, row % B, rm.n) : (size_t)(row % B)];
   const bool ok = lab64 >= 0 && lab64 < C;
   const int lab = ok ? (int)lab64 : -1;
   float m = -INFINITY;
@@ -347,12 +389,13 @@ bool head_gemm_supported(int G, int B, int K, int C) { return hg::supported(G, B
 
 hipError_t launch_head_gemm_logits(const float* x, const float* W, const float* bias, const int64_t* labels, int G,
                                    int B, int K, int C, float gscale, float* logits, float* dz, float* rowstat,
-                                   hipStream_t s) {
+                                   hipStream_t s, const int64_t* rows, long N) {
   hg::Plan pl;
-  if (!hg::make_plan(G, B, K, C, &pl)) return hipErrorInvalidValue;
+  if (!hg::make_plan(G, B, K, C, &pl) || (rows != nullptr && N < 1)) return hipErrorInvalidValue;
   if (x == nullptr || W == nullptr || bias == nullptr || labels == nullptr || logits == nullptr || rowstat == nullptr)
     return hipErrorInvalidValue;
-  if (!aligned16(x) || !aligned16(W) || !aligned16(logits) || (dz != nullptr && !aligned16(dz)))
+  // (a bank may sit at any 4-byte alignment: its rows are then staged 4 bytes at a time)
+  if ((rows == nullptr && !aligned16(x)) || !aligned16(W) || !aligned16(logits) || (dz != nullptr && !aligned16(dz)))
     return hipErrorInvalidValue;
   GemmParams p = {};
   p.a = operand(x, B, K, K, 1);
@@ -361,10 +404,22 @@ hipError_t launch_head_gemm_logits(const float* x, const float* W, const float* 
   p.G = G; p.B = B; p.C = C; p.K = K;
   p.out = logits;
   p.bias = bias;
-  hipLaunchKernelGGL((head_gemm_kernel<kVec, kVec, kLogits>), dim3(pl.nt.tiles), dim3(256), 0, s, p);
+  const RowMap rm = {rows, N};
+  const dim3 grid(pl.nt.tiles), rgrid(pl.row_blocks), blk(256);
+  if (rows == nullptr) {
+    hipLaunchKernelGGL((head_gemm_kernel<kVec, kVec, kLogits>), grid, blk, 0, s, p, rm);
+    SDX_LAUNCH_CHECK();
+    hipLaunchKernelGGL(ce_rows_kernel<false>, rgrid, blk, 0, s, logits, labels, rm, pl.rows, B, C, gscale, dz,
+                       rowstat);
+    SDX_LAUNCH_CHECK();
+    return hipSuccess;
+  }
+  if (aligned16(x))   // K = 64·j: every bank row is 16-byte aligned when the bank is
+    hipLaunchKernelGGL((head_gemm_kernel<kVec, kVec, kLogits, kMapOut>), grid, blk, 0, s, p, rm);
+  else
+    hipLaunchKernelGGL((head_gemm_kernel<kRowScalar, kVec, kLogits, kMapOut>), grid, blk, 0, s, p, rm);
   SDX_LAUNCH_CHECK();
-  hipLaunchKernelGGL(ce_rows_kernel, dim3(pl.row_blocks), dim3(256), 0, s, logits, labels, pl.rows, B, C, gscale, dz,
-                     rowstat);
+  hipLaunchKernelGGL(ce_rows_kernel<true>, rgrid, blk, 0, s, logits, labels, rm, pl.rows, B, C, gscale, dz, rowstat);
   SDX_LAUNCH_CHECK();
   return hipSuccess;
 }
@@ -384,13 +439,14 @@ hipError_t launch_head_gemm_stats(int G, int B, int K, int C, const float* rowst
 
 hipError_t launch_head_gemm_sgd(const float* x, const float* dz, int G, int B, int K, int C, float* W, float* bias,
                                 float* bufW, float* bufb, const float* lrs, const float* wds, float mom, int first,
-                                const float* rowstat, float* stats, hipStream_t s) {
+                                const float* rowstat, float* stats, hipStream_t s, const int64_t* rows, long N) {
   hg::Plan pl;
-  if (!hg::make_plan(G, B, K, C, &pl)) return hipErrorInvalidValue;
+  if (!hg::make_plan(G, B, K, C, &pl) || (rows != nullptr && N < 1)) return hipErrorInvalidValue;
   if (x == nullptr || dz == nullptr || W == nullptr || bias == nullptr || bufW == nullptr || bufb == nullptr ||
       lrs == nullptr || wds == nullptr || rowstat == nullptr || stats == nullptr)
     return hipErrorInvalidValue;
-  if (!aligned16(x) || !aligned16(dz) || !aligned16(W) || !aligned16(bufW)) return hipErrorInvalidValue;
+  if ((rows == nullptr && !aligned16(x)) || !aligned16(dz) || !aligned16(W) || !aligned16(bufW))
+    return hipErrorInvalidValue;
   GemmParams p = {};
   p.a = operand(dz, G * C, B, 1, C, C, (long)B * C);
   p.b = operand(x, K, B, 1, K);
@@ -404,7 +460,12 @@ hipError_t launch_head_gemm_sgd(const float* x, const float* dz, int G, int B, i
   p.mom = mom;
   p.first = first;
   p.dz = dz; p.rowstat = rowstat; p.stats = stats;
-  hipLaunchKernelGGL((head_gemm_kernel<kTrans, kTrans, kSgd>), dim3(pl.tn.tiles + pl.bias_blocks), dim3(256), 0, s, p);
+  const dim3 grid(pl.tn.tiles + pl.bias_blocks);
+  if (rows == nullptr)
+    hipLaunchKernelGGL((head_gemm_kernel<kTrans, kTrans, kSgd>), grid, dim3(256), 0, s, p, RowMap{nullptr, 0});
+  else
+    hipLaunchKernelGGL((head_gemm_kernel<kTrans, kTrans, kSgd, kMapNone, kMapRed>), grid, dim3(256), 0, s, p,
+                       RowMap{rows, N});
   SDX_LAUNCH_CHECK();
   return hipSuccess;
 }
@@ -428,7 +489,8 @@ hipError_t launch_head_gemm_bwd(const float* x, const float* dz, const float* W,
     p.b = operand(W, K, C, 1, K);
     set_form(p, pl.nn);
     p.out = dX;
-    hipLaunchKernelGGL((head_gemm_kernel<kRowScalar, kTrans, kDx>), dim3(pl.nn.tiles), dim3(256), 0, s, p);
+    hipLaunchKernelGGL((head_gemm_kernel<kRowScalar, kTrans, kDx>), dim3(pl.nn.tiles), dim3(256), 0, s, p,
+                       RowMap{nullptr, 0});
     SDX_LAUNCH_CHECK();
   }
   p.rowstat = rowstat; p.stats = stats; p.loss = loss;
@@ -440,7 +502,7 @@ hipError_t launch_head_gemm_bwd(const float* x, const float* dz, const float* W,
     p.bvec = db;
     p.dz = dz;
     hipLaunchKernelGGL((head_gemm_kernel<kTrans, kTrans, kDw>), dim3(pl.tn.tiles + pl.bias_blocks), dim3(256), 0, s,
-                       p);
+                       p, RowMap{nullptr, 0});
   } else {
     hipLaunchKernelGGL(head_stats_kernel, dim3(1), dim3(256), 0, s, p);
   }

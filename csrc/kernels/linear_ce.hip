@@ -51,11 +51,14 @@ __device__ __forceinline__ float lane_max(float v) {
   return v;
 }
 
-// KJ = K / 64 feature columns per lane
-template <int KJ>
+// KJ = K / 64 feature columns per lane. ROWS: batch row b is row rows[b] of the bank x [N][K],
+// labels [N] (the row-indexed step: no gathered copy of the batch is ever made); the plain
+// instantiation takes rows = nullptr, N = 0 and never reads them
+template <int KJ, bool ROWS>
 __global__ __launch_bounds__(256) void linear_ce_fwd_kernel(const float* __restrict__ x, const float* __restrict__ W,
                                                             const float* __restrict__ bias,
-                                                            const int64_t* __restrict__ labels, int B, int C,
+                                                            const int64_t* __restrict__ labels,
+                                                            const int64_t* __restrict__ rows, long N, int B, int C,
                                                             float gscale, float* __restrict__ logits,
                                                             float* __restrict__ dz, float* __restrict__ rowstat) {
   constexpr int K = 64 * KJ;
@@ -66,8 +69,10 @@ __global__ __launch_bounds__(256) void linear_ce_fwd_kernel(const float* __restr
 #pragma unroll
   for (int r = 0; r < kRows; ++r) {
     const int row = r0 + r;
+    size_t src = (size_t)row;
+    if constexpr (ROWS) src = row < B ? bank_row(rows, row, N) : 0;
 #pragma unroll
-    for (int j = 0; j < KJ; ++j) xv[r][j] = row < B ? x[(size_t)row * K + 64 * j + lane] : 0.f;
+    for (int j = 0; j < KJ; ++j) xv[r][j] = row < B ? x[src * K + 64 * j + lane] : 0.f;
   }
   for (int c = wv; c < C; c += 4) {
     const float* wr = W + (size_t)c * K;
@@ -89,7 +94,7 @@ __global__ __launch_bounds__(256) void linear_ce_fwd_kernel(const float* __restr
   // row softmax / cross-entropy / top-k hits: wave wv owns row r0 + wv
   const int row = r0 + wv;
   if (row >= B) return;
-  const int lab = (int)labels[row];
+  const int lab = (int)labels[ROWS ? bank_row(rows, row, N) : (size_t)row];
   float m = -INFINITY;
   for (int c = lane; c < C; c += 64) m = fmaxf(m, z[wv][c]);
   m = lane_max(m);
@@ -114,12 +119,16 @@ __global__ __launch_bounds__(256) void linear_ce_fwd_kernel(const float* __restr
   }
 }
 
-// grid: ceil(C*K/4 / 256) weight blocks + 1 (bias + statistics); W == nullptr: statistics only
+// grid: ceil(C*K/4 / 256) weight blocks + 1 (bias + statistics); W == nullptr: statistics only.
+// RM (RowMode): batch row b of x is bank row rows[b], read as one float4 or, for a bank whose
+// rows are not 16-byte aligned, as 4 floats
+template <int RM>
 __global__ __launch_bounds__(256) void linear_ce_sgd_kernel(const float* __restrict__ x, const float* __restrict__ dz,
-                                                            int B, int K, int C, float* __restrict__ W,
-                                                            float* __restrict__ bias, float* __restrict__ bufW,
-                                                            float* __restrict__ bufb, float lr, float mom, float wd,
-                                                            int first, const float* __restrict__ rowstat,
+                                                            const int64_t* __restrict__ rows, long N, int B, int K,
+                                                            int C, float* __restrict__ W, float* __restrict__ bias,
+                                                            float* __restrict__ bufW, float* __restrict__ bufb,
+                                                            float lr, float mom, float wd, int first,
+                                                            const float* __restrict__ rowstat,
                                                             float* __restrict__ stats) {
   const int nw4 = C * K / 4;
   if (blockIdx.x + 1 < gridDim.x) {
@@ -130,7 +139,7 @@ __global__ __launch_bounds__(256) void linear_ce_sgd_kernel(const float* __restr
     float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int b = 0; b < B; ++b) {
       const float d = dz[(size_t)b * C + c];
-      const float4 v = *reinterpret_cast<const float4*>(x + (size_t)b * K + k);
+      const float4 v = load_x4<RM>(x, rows, N, b, K, k);
       g.x = fmaf(d, v.x, g.x);
       g.y = fmaf(d, v.y, g.y);
       g.z = fmaf(d, v.z, g.z);
@@ -249,14 +258,19 @@ __global__ __launch_bounds__(256) void ce_head_bwd_kernel(const float* __restric
 bool linear_ce_supported(int K, int C) { return K % 64 == 0 && K >= 64 && K <= 64 * 32 && C >= 1 && C <= kMaxClasses; }
 
 hipError_t launch_linear_ce_fwd(const float* x, const float* W, const float* bias, const int64_t* labels, int B,
-                                int K, int C, float gscale, float* logits, float* dz, float* rowstat, hipStream_t s) {
-  if (!linear_ce_supported(K, C) || B < 1) return hipErrorInvalidValue;
+                                int K, int C, float gscale, float* logits, float* dz, float* rowstat, hipStream_t s,
+                                const int64_t* rows, long N) {
+  if (!linear_ce_supported(K, C) || B < 1 || (rows != nullptr && N < 1)) return hipErrorInvalidValue;
   const dim3 grid((B + kRows - 1) / kRows), blk(256);
   switch (K / 64) {
 #define SDX_LCE(KJ)                                                                                          \
   case KJ:                                                                                                  \
-    hipLaunchKernelGGL((linear_ce_fwd_kernel<KJ>), grid, blk, 0, s, x, W, bias, labels, B, C, gscale, logits, dz, \
-                       rowstat);                                                                            \
+    if (rows != nullptr)                                                                                    \
+      hipLaunchKernelGGL((linear_ce_fwd_kernel<KJ, true>), grid, blk, 0, s, x, W, bias, labels, rows, N, B, C, \
+                         gscale, logits, dz, rowstat);                                                      \
+    else                                                                                                    \
+      hipLaunchKernelGGL((linear_ce_fwd_kernel<KJ, false>), grid, blk, 0, s, x, W, bias, labels, rows, N, B, C, \
+                         gscale, logits, dz, rowstat);                                                      \
     break;
     SDX_LCE(1) SDX_LCE(2) SDX_LCE(4) SDX_LCE(8) SDX_LCE(16) SDX_LCE(32)
 #undef SDX_LCE
@@ -269,12 +283,19 @@ hipError_t launch_linear_ce_fwd(const float* x, const float* W, const float* bia
 
 hipError_t launch_linear_ce_sgd(const float* x, const float* dz, int B, int K, int C, float* W, float* bias,
                                 float* bufW, float* bufb, float lr, float mom, float wd, int first,
-                                const float* rowstat, float* stats, hipStream_t s) {
-  if (B < 1 || K % 4 != 0 || C < 1) return hipErrorInvalidValue;
+                                const float* rowstat, float* stats, hipStream_t s, const int64_t* rows, long N) {
+  if (B < 1 || K % 4 != 0 || C < 1 || (rows != nullptr && N < 1)) return hipErrorInvalidValue;
   const int nw4 = C * K / 4;
   const dim3 grid(W != nullptr ? (nw4 + 255) / 256 + 1 : 1), blk(256);
-  hipLaunchKernelGGL(linear_ce_sgd_kernel, grid, blk, 0, s, x, dz, B, K, C, W, bias, bufW, bufb, lr, mom, wd, first,
-                     rowstat, stats);
+  if (rows == nullptr)
+    hipLaunchKernelGGL((linear_ce_sgd_kernel<kRowsNone>), grid, blk, 0, s, x, dz, rows, N, B, K, C, W, bias, bufW,
+                       bufb, lr, mom, wd, first, rowstat, stats);
+  else if (((uintptr_t)x & 15) == 0)
+    hipLaunchKernelGGL((linear_ce_sgd_kernel<kRowsVec>), grid, blk, 0, s, x, dz, rows, N, B, K, C, W, bias, bufW,
+                       bufb, lr, mom, wd, first, rowstat, stats);
+  else
+    hipLaunchKernelGGL((linear_ce_sgd_kernel<kRowsScalar>), grid, blk, 0, s, x, dz, rows, N, B, K, C, W, bias, bufW,
+                       bufb, lr, mom, wd, first, rowstat, stats);
   SDX_LAUNCH_CHECK();
   return hipSuccess;
 }

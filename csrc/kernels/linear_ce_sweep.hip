@@ -51,12 +51,13 @@ __device__ __forceinline__ float lane_max(float v) {
   return v;
 }
 
-// KJ = K / 64 feature columns per lane
-template <int KJ>
+// KJ = K / 64 feature columns per lane. ROWS: batch row b is row rows[b] of the bank x [N][K],
+// labels [N], as in linear_ce.hip (the plain instantiation takes rows = nullptr, N = 0 unread)
+template <int KJ, bool ROWS>
 __global__ __launch_bounds__(256) void linear_ce_sweep_fwd_kernel(
     const float* __restrict__ x, const float* __restrict__ W, const float* __restrict__ bias,
-    const int64_t* __restrict__ labels, int G, int B, int C, float gscale, float* __restrict__ logits,
-    float* __restrict__ dz, float* __restrict__ rowstat) {
+    const int64_t* __restrict__ labels, const int64_t* __restrict__ rows, long N, int G, int B, int C, float gscale,
+    float* __restrict__ logits, float* __restrict__ dz, float* __restrict__ rowstat) {
   constexpr int K = 64 * KJ;
   __shared__ float z[kRows][kMaxClasses];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -65,12 +66,14 @@ __global__ __launch_bounds__(256) void linear_ce_sweep_fwd_kernel(
 #pragma unroll
   for (int r = 0; r < kRows; ++r) {
     const int row = r0 + r;
+    size_t src = (size_t)row;
+    if constexpr (ROWS) src = row < B ? bank_row(rows, row, N) : 0;
 #pragma unroll
-    for (int j = 0; j < KJ; ++j) xv[r][j] = row < B ? x[(size_t)row * K + 64 * j + lane] : 0.f;
+    for (int j = 0; j < KJ; ++j) xv[r][j] = row < B ? x[src * K + 64 * j + lane] : 0.f;
   }
   // wave wv owns row r0 + wv in every head's softmax
   const int row = r0 + wv;
-  const int lab = row < B ? (int)labels[row] : -1;
+  const int lab = row < B ? (int)labels[ROWS ? bank_row(rows, row, N) : (size_t)row] : -1;
   for (int g = 0; g < G; ++g) {
     const float* Wg = W + (size_t)g * C * K;
     const float* bg = bias + (size_t)g * C;
@@ -121,12 +124,13 @@ __global__ __launch_bounds__(256) void linear_ce_sweep_fwd_kernel(
   }
 }
 
-// grid: ceil(C*K/4 / 256) weight blocks + 1 (biases + statistics); W == nullptr: statistics only
-template <int G>
+// grid: ceil(C*K/4 / 256) weight blocks + 1 (biases + statistics); W == nullptr: statistics only.
+// RM (RowMode, common.h): where batch row b of x comes from
+template <int G, int RM>
 __global__ __launch_bounds__(256) void linear_ce_sweep_sgd_kernel(
-    const float* __restrict__ x, const float* __restrict__ dz, int B, int K, int C, float* __restrict__ W,
-    float* __restrict__ bias, float* __restrict__ bufW, float* __restrict__ bufb, SweepHyper hp, float mom, int first,
-    const float* __restrict__ rowstat, float* __restrict__ stats) {
+    const float* __restrict__ x, const float* __restrict__ dz, const int64_t* __restrict__ rows, long N, int B, int K,
+    int C, float* __restrict__ W, float* __restrict__ bias, float* __restrict__ bufW, float* __restrict__ bufb,
+    SweepHyper hp, float mom, int first, const float* __restrict__ rowstat, float* __restrict__ stats) {
   const int nw4 = C * K / 4;
   const size_t bc = (size_t)B * C;
   if (blockIdx.x + 1 < gridDim.x) {
@@ -138,7 +142,7 @@ __global__ __launch_bounds__(256) void linear_ce_sweep_sgd_kernel(
 #pragma unroll
     for (int h = 0; h < G; ++h) g[h] = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int b = 0; b < B; ++b) {
-      const float4 v = *reinterpret_cast<const float4*>(x + (size_t)b * K + k);
+      const float4 v = load_x4<RM>(x, rows, N, b, K, k);
 #pragma unroll
       for (int h = 0; h < G; ++h) {
         const float d = dz[h * bc + (size_t)b * C + c];
@@ -207,17 +211,22 @@ bool linear_ce_sweep_supported(int G, int K, int C) { return sweep_shape_ok(G, 1
 
 hipError_t launch_linear_ce_sweep_fwd(const float* x, const float* W, const float* bias, const int64_t* labels, int G,
                                       int B, int K, int C, float gscale, float* logits, float* dz, float* rowstat,
-                                      hipStream_t s) {
-  if (!sweep_shape_ok(G, B, K, C)) return hipErrorInvalidValue;
+                                      hipStream_t s, const int64_t* rows, long N) {
+  if (!sweep_shape_ok(G, B, K, C) || (rows != nullptr && N < 1)) return hipErrorInvalidValue;
   if (x == nullptr || W == nullptr || bias == nullptr || labels == nullptr || logits == nullptr || rowstat == nullptr)
     return hipErrorInvalidValue;
-  if (((uintptr_t)x | (uintptr_t)W) & 15) return hipErrorInvalidValue;
+  // (a bank is read 4 bytes at a time here: any alignment)
+  if (((rows == nullptr ? (uintptr_t)x : 0) | (uintptr_t)W) & 15) return hipErrorInvalidValue;
   const dim3 grid((B + kRows - 1) / kRows), blk(256);
   switch (K / 64) {
 #define SDX_LCS(KJ)                                                                                              \
   case KJ:                                                                                                      \
-    hipLaunchKernelGGL((linear_ce_sweep_fwd_kernel<KJ>), grid, blk, 0, s, x, W, bias, labels, G, B, C, gscale,   \
-                       logits, dz, rowstat);                                                                    \
+    if (rows != nullptr)                                                                                        \
+      hipLaunchKernelGGL((linear_ce_sweep_fwd_kernel<KJ, true>), grid, blk, 0, s, x, W, bias, labels, rows, N, G, \
+                         B, C, gscale, logits, dz, rowstat);                                                    \
+    else                                                                                                        \
+      hipLaunchKernelGGL((linear_ce_sweep_fwd_kernel<KJ, false>), grid, blk, 0, s, x, W, bias, labels, rows, N, G, \
+                         B, C, gscale, logits, dz, rowstat);                                                    \
     break;
     SDX_LCS(1) SDX_LCS(2) SDX_LCS(4) SDX_LCS(8) SDX_LCS(16) SDX_LCS(32)
 #undef SDX_LCS
@@ -230,8 +239,9 @@ hipError_t launch_linear_ce_sweep_fwd(const float* x, const float* W, const floa
 
 hipError_t launch_linear_ce_sweep_sgd(const float* x, const float* dz, int G, int B, int K, int C, float* W,
                                       float* bias, float* bufW, float* bufb, const float* lrs, const float* wds,
-                                      float mom, int first, const float* rowstat, float* stats, hipStream_t s) {
-  if (!sweep_shape_ok(G, B, K, C)) return hipErrorInvalidValue;
+                                      float mom, int first, const float* rowstat, float* stats, hipStream_t s,
+                                      const int64_t* rows, long N) {
+  if (!sweep_shape_ok(G, B, K, C) || (rows != nullptr && N < 1)) return hipErrorInvalidValue;
   if (rowstat == nullptr || stats == nullptr) return hipErrorInvalidValue;
   SweepHyper hp = {};
   if (W != nullptr) {
@@ -239,7 +249,7 @@ hipError_t launch_linear_ce_sweep_sgd(const float* x, const float* dz, int G, in
     if (x == nullptr || dz == nullptr || bias == nullptr || bufW == nullptr || bufb == nullptr || lrs == nullptr ||
         wds == nullptr)
       return hipErrorInvalidValue;
-    if (((uintptr_t)x | (uintptr_t)W | (uintptr_t)bufW) & 15) return hipErrorInvalidValue;
+    if (((rows == nullptr ? (uintptr_t)x : 0) | (uintptr_t)W | (uintptr_t)bufW) & 15) return hipErrorInvalidValue;
     for (int h = 0; h < G; ++h) {
       hp.lr[h] = lrs[h];
       hp.wd[h] = wds[h];
@@ -250,8 +260,15 @@ hipError_t launch_linear_ce_sweep_sgd(const float* x, const float* dz, int G, in
   switch (G) {
 #define SDX_LCS(GG)                                                                                              \
   case GG:                                                                                                      \
-    hipLaunchKernelGGL((linear_ce_sweep_sgd_kernel<GG>), grid, blk, 0, s, x, dz, B, K, C, W, bias, bufW, bufb,   \
-                       hp, mom, first, rowstat, stats);                                                         \
+    if (rows == nullptr)                                                                                        \
+      hipLaunchKernelGGL((linear_ce_sweep_sgd_kernel<GG, kRowsNone>), grid, blk, 0, s, x, dz, rows, N, B, K, C,  \
+                         W, bias, bufW, bufb, hp, mom, first, rowstat, stats);                                  \
+    else if (((uintptr_t)x & 15) == 0)                                                                          \
+      hipLaunchKernelGGL((linear_ce_sweep_sgd_kernel<GG, kRowsVec>), grid, blk, 0, s, x, dz, rows, N, B, K, C,   \
+                         W, bias, bufW, bufb, hp, mom, first, rowstat, stats);                                  \
+    else                                                                                                        \
+      hipLaunchKernelGGL((linear_ce_sweep_sgd_kernel<GG, kRowsScalar>), grid, blk, 0, s, x, dz, rows, N, B, K,   \
+                         C, W, bias, bufW, bufb, hp, mom, first, rowstat, stats);                               \
     break;
     SDX_LCS(1) SDX_LCS(2) SDX_LCS(3) SDX_LCS(4) SDX_LCS(5) SDX_LCS(6) SDX_LCS(7) SDX_LCS(8)
     SDX_LCS(9) SDX_LCS(10) SDX_LCS(11) SDX_LCS(12) SDX_LCS(13) SDX_LCS(14) SDX_LCS(15) SDX_LCS(16)

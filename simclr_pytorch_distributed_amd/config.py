@@ -17,7 +17,8 @@ Additions (new flags only; no reference flag changes meaning):
 ``--blur_p`` / ``--blur_kernel`` / ``--blur_sigma`` (Gaussian-blur augmentation, data/augment.py),
 ``--val_folder`` / ``--resize`` (ImageFolder evaluation: Resize + CenterCrop on the GPU; the linear
 probe also takes ``--dataset path`` with ``--size`` / ``--mean`` / ``--std``),
-``--sweep_lr`` / ``--sweep_wd`` (linear probe: one classifier per (lr, wd) pair on one encoder pass).
+``--sweep_lr`` / ``--sweep_wd`` (linear probe: one classifier per (lr, wd) pair on one encoder pass),
+``--cache_features`` / ``--cache_views`` (linear probe: encode the frozen encoder's features once).
 Fixes: ``--num_workers`` is honoured (Q6): it sizes the image-decode thread pool of
 ``dataset=path`` and the CPU augmentation threads of ``--gpu_aug 0`` (the default pipeline
 is the GPU kernel, which needs no workers); ``dataset=path`` parses ``--mean/--std``
@@ -322,18 +323,29 @@ def linear_parser() -> argparse.ArgumentParser:
     g.add_argument("--sweep_wd", type=float, nargs="+", default=None, metavar="WD",
                    help="weight decays of the sweep (absent: --weight_decay)")
     _add_head_gemm_flag(g)
+    g.add_argument("--cache_features", type=str, default=argparse.SUPPRESS, choices=list(CACHE_MODES),
+                   help="the encoder is frozen: val = encode the validation store once and validate every epoch on "
+                        "those features (results identical to off); all = also train on a feature bank of the "
+                        "training store extracted once (see --cache_views); default off")
+    g.add_argument("--cache_views", type=int, default=argparse.SUPPRESS, metavar="V",
+                   help="with --cache_features all: 0 = one bank row per image under the evaluation transform (no "
+                        "training augmentation); V >= 1 = V rows per image, independent draws of the training "
+                        "augmentation, epoch e using view (e - 1) mod V; default 0")
     _add_common_new_flags(p)
     return p
 
 
 SWEEP_MAX_HEADS = 16
+CACHE_MODES = ("off", "val", "all")
 
 
 class _HeadOptions(argparse.Namespace):
-    """``opt.head_gemm`` reads "fma" when the flag is absent without becoming an entry of
-    ``vars(opt)``: a run that does not use the flag keeps the namespace (and the saved options) it
-    had before the flag existed."""
+    """``opt.head_gemm`` reads "fma" (and ``opt.cache_features`` "off", ``opt.cache_views`` 0) when
+    the flag is absent without becoming an entry of ``vars(opt)``: a run that does not use the flag
+    keeps the namespace (and the saved options) it had before the flag existed."""
     head_gemm = "fma"
+    cache_features = "off"
+    cache_views = 0
 
 
 def _add_head_gemm_flag(g):
@@ -381,6 +393,11 @@ def parse_linear(argv: Optional[Sequence[str]] = None, make_dirs: bool = True,
     parser = linear_parser()
     opt = parser.parse_args(argv, namespace=_HeadOptions())
     _sweep_heads(parser, opt)
+    if opt.cache_views < 0:
+        parser.error(f"--cache_views {opt.cache_views}: the number of cached views cannot be negative")
+    if opt.cache_views > 0 and opt.cache_features != "all":
+        parser.error(f"--cache_views {opt.cache_views} needs --cache_features all (got {opt.cache_features}): "
+                     "only the training bank has views")
     if opt.knn_k < 1 or not opt.knn_t > 0:
         raise ValueError("--knn_k >= 1 and --knn_t > 0 are required")
     if opt.size < 1:

@@ -17,6 +17,15 @@ Sweep (``--sweep_lr`` / ``--sweep_wd``): G classifiers, one per (lr, wd) pair, a
 the same encoder pass, each on the reference schedule for its own base lr; on the native path
 all of them are the same two launches (ops/linear_probe.py ``NativeLinearSweep``), elsewhere a
 loop over G torch classifiers. Every head computes what a single run with its settings computes.
+
+Feature cache (``--cache_features``): the encoder is frozen, so its features can be extracted once.
+``val``: the validation store is encoded before epoch 1, in the batches ``validate`` uses, and every
+epoch validates on slices of those features — the same numbers as ``off``. ``all``: the training
+store is encoded once too, into a feature bank (``--cache_views`` 0: one row per image under the
+evaluation transform; V >= 1: V draws of the training augmentation per image, epoch e on view
+(e − 1) mod V), and a training step reads its batch from the bank by the sampler's indices; on the
+native path inside the classifier's own launches (ops/linear_probe.py ``train_batch_rows``),
+elsewhere as ``bank[rows]`` in front of the step that runs without a cache.
 """
 from __future__ import annotations
 
@@ -42,6 +51,13 @@ from ..utils.meters import AverageMeter, accuracy
 from ..utils.profiling import PhaseTimer
 from . import checkpoint as ckpt_mod
 from .base import resolve_backend, step_seed
+
+
+def free_memory(device: torch.device) -> Optional[int]:
+    """Bytes a new allocation on ``device`` can take (``torch.cuda.mem_get_info``); None: not known."""
+    if device.type != "cuda":
+        return None
+    return int(torch.cuda.mem_get_info(device)[0])
 
 
 class LinearEngine:
@@ -114,6 +130,66 @@ class LinearEngine:
         from ..utils.tb import Logger
         self.logger = Logger(opt.tb_folder, flush_secs=2)
         self.prof = PhaseTimer(getattr(opt, "profile", False), dev)
+        # --cache_features: the banks are extracted by prepare_cache, before the first epoch
+        self.cache = getattr(opt, "cache_features", "off")
+        self.cache_views = getattr(opt, "cache_views", 0)
+        self.val_bank: Optional[linear_probe.FeatureBank] = None
+        self.bank: Optional[linear_probe.FeatureBank] = None
+
+    @torch.no_grad()
+    def _extract(self, store, cfg, batch: int, views: int, seeded: bool) -> linear_probe.FeatureBank:
+        """The encoder's features of every image of ``store`` in index order, ``batch`` images per
+        encoder pass, ``views`` times over (view v of batch i drawn with the seed that training
+        step i of epoch v + 1 uses), written into one preallocated fp32 tensor."""
+        n, k = len(store), self.classifier.fc.in_features
+        feats = torch.empty(views * n, k, dtype=torch.float32, device=self.device)
+        ph = self.prof.phase
+        for v in range(views):
+            for i, s in enumerate(range(0, n, batch)):
+                idx = torch.arange(s, min(s + batch, n), device=self.device)
+                with ph("augment"):
+                    x = store.views(idx, cfg, step_seed(self.opt.seed, v + 1, i, 0) if seeded else 0)
+                with ph("encoder"):
+                    feats[v * n + s:v * n + s + idx.shape[0]] = self.encode(x)
+        return linear_probe.FeatureBank(feats, store.labels.long().repeat(views), n, views)
+
+    def prepare_cache(self):
+        """--cache_features val / all: the extraction pass, once; refuses before it encodes anything
+        when the banks do not fit the device."""
+        if self.cache == "off" or self.val_bank is not None:
+            return
+        opt = self.opt
+        k = self.classifier.fc.in_features
+        views = max(self.cache_views, 1)
+        shapes = [("val", len(self.val), 1)] + ([("train", len(self.train), views)] if self.cache == "all" else [])
+        need = sum(linear_probe.FeatureBank.nbytes(n * v, k) for _, n, v in shapes)
+        free = free_memory(self.device)
+        if free is not None and need > free:
+            raise RuntimeError(
+                "--cache_features {}: the feature banks ({}) need {} bytes, the device has {} free; use {}".format(
+                    self.cache, ", ".join(f"{nm} [{n * v}, {k}]" for nm, n, v in shapes), need, free,
+                    "--cache_features val, fewer --cache_views or a smaller dataset" if self.cache == "all"
+                    else "--cache_features off"))
+        t0 = time.time()
+        self.val_bank = self._extract(self.val, self.aug_val, opt.val_batch_size, 1, False)
+        if self.cache == "all":
+            cfg = self.aug_train if self.cache_views > 0 else self.aug_val
+            self.bank = self._extract(self.train, cfg, opt.batch_size, views, self.cache_views > 0)
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)
+        logging.info("feature cache ({}, {} views): {} fp32 + int64 labels, {} bytes, extracted in {:.2f}s".format(
+            self.cache, self.cache_views, ", ".join(f"{nm} bank [{n * v}, {k}]" for nm, n, v in shapes), need,
+            time.time() - t0))
+        if self.prof.enabled:
+            logging.info("phases (ms/batch, extraction): " + PhaseTimer.format(self.prof.summary()))
+
+    def _bank_batch(self, view, idx):
+        """(feats, labels, rows) of training batch ``idx`` of the bank view (feats [N, K], labels [N]):
+        the native classifiers read the rows in place; elsewhere the batch is gathered here."""
+        native = self.native_sweep if self.sweep else self.native_ce
+        if native is not None:
+            return view[0], view[1], idx
+        return view[0][idx], view[1][idx], None
 
     def head_state(self, g: int):
         """``LinearClassifier`` state dict of sweep head ``g``."""
@@ -121,12 +197,14 @@ class LinearEngine:
             return self.native_sweep.head_state(g)
         return {k: v.detach().clone() for k, v in self.classifiers[g].state_dict().items()}
 
-    def _classify_sweep(self, feats, labels, train: bool):
+    def _classify_sweep(self, feats, labels, train: bool, rows=None):
         """(logits [G, B, C], loss [G], acc1 [G], acc5 [G]) of a batch — device tensors; every
         value is computed as ``_classify`` computes a single classifier's."""
-        bsz = labels.shape[0]
+        bsz = labels.shape[0] if rows is None else rows.shape[0]
         if self.native_sweep is not None:
-            if train:
+            if rows is not None:
+                out, st = self.native_sweep.train_batch_rows(feats, labels, rows, self.head_lrs)
+            elif train:
                 out, st = self.native_sweep.train_batch(feats, labels, self.head_lrs)
             else:
                 out, st = self.native_sweep.eval_batch(feats, labels)
@@ -159,6 +237,8 @@ class LinearEngine:
         """``train_epoch`` for G heads: per-head (loss, acc1, acc5) lists; the window line reports head 0."""
         opt = self.opt
         G = len(self.sweep)
+        self.prepare_cache()
+        view = self.bank.epoch_view(epoch) if self.bank is not None else None     # --cache_features all
         self.sampler.set_epoch(epoch)
         iters = len(self.sampler)
         if opt.max_steps:
@@ -172,15 +252,21 @@ class LinearEngine:
                 break
             dtm.update(time.time() - end)
             ph = self.prof.phase
-            with ph("augment"):
-                x = self.train.views(idx, self.aug_train, step_seed(opt.seed, epoch, idx_i, 0))
-                labels = self.train.labels[idx]
-            bsz = labels.shape[0]
+            rows = None
+            if view is None:
+                with ph("augment"):
+                    x = self.train.views(idx, self.aug_train, step_seed(opt.seed, epoch, idx_i, 0))
+                    labels = self.train.labels[idx]
+            else:
+                with ph("gather"):
+                    feats, labels, rows = self._bank_batch(view, idx)
+            bsz = idx.shape[0]
             self._set_head_lrs([warmup_lr(o, epoch, idx_i, iters) for o in self.head_opts])
-            with ph("encoder"):
-                feats = self.encode(x)
+            if view is None:
+                with ph("encoder"):
+                    feats = self.encode(x)
             with ph("classifier"):
-                output, loss, acc1, acc5 = self._classify_sweep(feats, labels, True)
+                output, loss, acc1, acc5 = self._classify_sweep(feats, labels, True, rows)
                 win += torch.stack([loss.double() * bsz, acc1.double() * bsz, acc5.double() * bsz,
                                     torch.full((G,), float(bsz), dtype=torch.float64, device=self.device)], dim=1)
             bt.update(time.time() - end)
@@ -212,11 +298,10 @@ class LinearEngine:
         n = len(self.val)
         losses, top1, top5 = ([AverageMeter() for _ in range(G)] for _ in range(3))
         vb = opt.val_batch_size
+        self.prepare_cache()
         for i, s in enumerate(range(0, n, vb)):
-            idx = torch.arange(s, min(s + vb, n), device=self.device)
-            x = self.val.views(idx, self.aug_val, 0)
-            labels = self.val.labels[idx]
-            output, loss, acc1, acc5 = self._classify_sweep(self.encode(x), labels, False)
+            feats, labels = self._val_batch(s, min(s + vb, n))
+            output, loss, acc1, acc5 = self._classify_sweep(feats, labels, False)
             bsz = labels.shape[0]
             host = torch.stack([loss, acc1, acc5], dim=1).tolist()
             for g in range(G):
@@ -237,6 +322,7 @@ class LinearEngine:
         res = [{"lr": lr, "wd": wd, "best_acc": 0.0, "best_acc5": 0.0, "best_epoch": 0} for lr, wd in self.sweep]
         if getattr(opt, "knn", False):
             self.knn_eval()
+        self.prepare_cache()
         for epoch in range(1, opt.epochs + 1):
             self._set_head_lrs([lr_at_epoch(o, epoch) for o in self.head_opts])
             t1 = time.time()
@@ -262,11 +348,15 @@ class LinearEngine:
         self.logger.close()
         return best["best_acc"], best["best_acc5"]
 
-    def _classify(self, feats, labels, train: bool):
-        """(logits, loss, acc1, acc5) of a batch — device tensors; train: + the SGD step."""
-        bsz = labels.shape[0]
+    def _classify(self, feats, labels, train: bool, rows=None):
+        """(logits, loss, acc1, acc5) of a batch — device tensors; train: + the SGD step.
+        ``rows`` (native training only, ``_bank_batch``): the batch is rows ``rows`` of the bank
+        ``feats`` / ``labels``."""
+        bsz = labels.shape[0] if rows is None else rows.shape[0]
         if self.native_ce is not None:
-            if train:
+            if rows is not None:
+                out, st = self.native_ce.train_batch_rows(feats, labels, rows, self.optimizer.param_groups[0]["lr"])
+            elif train:
                 out, st = self.native_ce.train_batch(feats, labels, self.optimizer.param_groups[0]["lr"])
             else:
                 out, st = self.native_ce.eval_batch(feats, labels)
@@ -285,6 +375,8 @@ class LinearEngine:
             return self._train_epoch_sweep(epoch)
         opt = self.opt
         self.classifier.train()
+        self.prepare_cache()
+        view = self.bank.epoch_view(epoch) if self.bank is not None else None     # --cache_features all
         self.sampler.set_epoch(epoch)
         iters = len(self.sampler)
         if opt.max_steps:
@@ -299,15 +391,21 @@ class LinearEngine:
                 break
             dtm.update(time.time() - end)
             ph = self.prof.phase
-            with ph("augment"):
-                x = self.train.views(idx, self.aug_train, step_seed(opt.seed, epoch, idx_i, 0))
-                labels = self.train.labels[idx]
-            bsz = labels.shape[0]
+            rows = None
+            if view is None:
+                with ph("augment"):
+                    x = self.train.views(idx, self.aug_train, step_seed(opt.seed, epoch, idx_i, 0))
+                    labels = self.train.labels[idx]
+            else:
+                with ph("gather"):
+                    feats, labels, rows = self._bank_batch(view, idx)
+            bsz = idx.shape[0]
             warmup_learning_rate(opt, epoch, idx_i, iters, self.optimizer)
-            with ph("encoder"):
-                feats = self.encode(x)
+            if view is None:
+                with ph("encoder"):
+                    feats = self.encode(x)
             with ph("classifier"):
-                output, loss, acc1, acc5 = self._classify(feats, labels, True)
+                output, loss, acc1, acc5 = self._classify(feats, labels, True, rows)
                 win += torch.stack([loss.double() * bsz, acc1.double() * bsz, acc5.double() * bsz,
                                     torch.tensor(float(bsz), dtype=torch.float64, device=self.device)])
             bt.update(time.time() - end)
@@ -338,11 +436,10 @@ class LinearEngine:
         n = len(self.val)
         losses, top1, top5 = AverageMeter(), AverageMeter(), AverageMeter()
         vb = opt.val_batch_size
+        self.prepare_cache()
         for i, s in enumerate(range(0, n, vb)):
-            idx = torch.arange(s, min(s + vb, n), device=self.device)
-            x = self.val.views(idx, self.aug_val, 0)
-            labels = self.val.labels[idx]
-            output, loss, acc1, acc5 = self._classify(self.encode(x), labels, False)
+            feats, labels = self._val_batch(s, min(s + vb, n))
+            output, loss, acc1, acc5 = self._classify(feats, labels, False)
             bsz = labels.shape[0]
             losses.update(loss.item(), bsz)
             top1.update(acc1.item(), bsz)
@@ -353,6 +450,15 @@ class LinearEngine:
                                  i, (n + vb - 1) // vb, loss=losses, top1=top1))
         logging.info(" * Acc@1 {top1.avg:.3f}, Acc@5 {top5.avg:.3f}".format(top1=top1, top5=top5))
         return losses.avg, top1.avg, top5.avg
+
+    def _val_batch(self, s: int, e: int):
+        """(feats, labels) of validation images s..e-1: encoded now, or (--cache_features) a slice
+        of the features the same batch had in the extraction pass."""
+        if self.val_bank is not None:
+            return self.val_bank.feats[s:e], self.val_bank.labels[s:e]
+        idx = torch.arange(s, e, device=self.device)
+        x = self.val.views(idx, self.aug_val, 0)
+        return self.encode(x), self.val.labels[idx]
 
     def knn_eval(self):
         """--knn: weighted k-NN accuracy of the loaded encoder (tags knn/val_acc1, knn/val_acc5 at step 0)."""
@@ -374,6 +480,7 @@ class LinearEngine:
         best_acc, best_acc5 = 0.0, 0.0
         if getattr(opt, "knn", False):
             self.knn_eval()
+        self.prepare_cache()
         for epoch in range(1, opt.epochs + 1):
             adjust_learning_rate(opt, self.optimizer, epoch)
             t1 = time.time()

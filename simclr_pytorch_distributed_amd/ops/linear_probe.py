@@ -13,6 +13,9 @@ networks/resnet_big.py:196-204).
 * :class:`NativeLinearSweep` — G such classifiers, each with its own learning rate and weight
   decay, on one feature batch in the same two launches (csrc/kernels/linear_ce_sweep.hip): a
   hyper-parameter sweep of the probe pays for the encoder once.
+* :class:`FeatureBank` — the frozen encoder's features of a whole store, extracted once
+  (``--cache_features``); ``train_batch_rows`` / ``eval_batch_rows`` of the two classes above
+  read a batch from it by row index inside the same launches (no gather, no copy).
 """
 from __future__ import annotations
 
@@ -138,8 +141,26 @@ class NativeLinearCE:
                          None, None, 0.0, 0.0, 0.0, False, False)
         return out[0], out[1]
 
-    def _op(self):
+    @torch.no_grad()
+    def train_batch_rows(self, bank: torch.Tensor, bank_labels: torch.Tensor, rows: torch.Tensor, lr: float):
+        """``train_batch(bank[rows], bank_labels[rows], lr)``, bit for bit, with the rows read from
+        the bank in place: ``bank`` fp32 [N, K], ``bank_labels`` int64 [N], ``rows`` int64 [B] on
+        the device, every value in [0, N)."""
+        out = self._op(True)(bank, self.W.data, self.b.data, bank_labels, rows, self.bufW, self.bufb,
+                             float(lr), self.momentum, self.weight_decay, self.first, True)
+        self.first = False
+        return out[0], out[1]
+
+    @torch.no_grad()
+    def eval_batch_rows(self, bank: torch.Tensor, bank_labels: torch.Tensor, rows: torch.Tensor):
+        out = self._op(True)(bank, self.W.data, self.b.data, bank_labels, rows, None, None, 0.0, 0.0, 0.0,
+                             False, False)
+        return out[0], out[1]
+
+    def _op(self, rows: bool = False):
         m = _ext.require()
+        if rows:
+            return m.linear_ce_step_mfma_rows if self.gemm == "mfma" else m.linear_ce_step_rows
         return m.linear_ce_step_mfma if self.gemm == "mfma" else m.linear_ce_step
 
 
@@ -183,13 +204,58 @@ class NativeLinearSweep:
                          None, None, zeros, 0.0, zeros, False, False)
         return out[0], out[1]
 
-    def _op(self):
+    @torch.no_grad()
+    def train_batch_rows(self, bank: torch.Tensor, bank_labels: torch.Tensor, rows: torch.Tensor,
+                         lrs: Sequence[float]):
+        """``train_batch(bank[rows], bank_labels[rows], lrs)``, bit for bit, the rows read in place
+        (see :meth:`NativeLinearCE.train_batch_rows`)."""
+        out = self._op(True)(bank, self.W, self.b, bank_labels, rows, self.bufW, self.bufb,
+                             [float(v) for v in lrs], self.momentum, self.weight_decays, self.first, True)
+        self.first = False
+        return out[0], out[1]
+
+    @torch.no_grad()
+    def eval_batch_rows(self, bank: torch.Tensor, bank_labels: torch.Tensor, rows: torch.Tensor):
+        zeros = [0.0] * self.G
+        out = self._op(True)(bank, self.W, self.b, bank_labels, rows, None, None, zeros, 0.0, zeros, False, False)
+        return out[0], out[1]
+
+    def _op(self, rows: bool = False):
         m = _ext.require()
+        if rows:
+            return m.linear_ce_sweep_step_mfma_rows if self.gemm == "mfma" else m.linear_ce_sweep_step_rows
         return m.linear_ce_sweep_step_mfma if self.gemm == "mfma" else m.linear_ce_sweep_step
 
     def head_state(self, g: int) -> Dict[str, torch.Tensor]:
         """``LinearClassifier`` state dict of head ``g``."""
         return {"fc.weight": self.W[g].clone(), "fc.bias": self.b[g].clone()}
+
+
+class FeatureBank:
+    """Features of a store under the frozen encoder, extracted once: ``feats`` fp32 [V·N, K] with
+    row ``v·N + i`` = view ``v`` of image ``i`` (one view: the evaluation transform), ``labels``
+    int64 [V·N] repeated alike, so a row index addresses both."""
+
+    def __init__(self, feats: torch.Tensor, labels: torch.Tensor, n_images: int, views: int = 1):
+        if feats.shape[0] != n_images * views or labels.shape[0] != feats.shape[0]:
+            raise ValueError("a bank holds views x images rows of features and as many labels")
+        self.feats, self.labels, self.n, self.views = feats, labels, int(n_images), int(views)
+
+    def rows_for(self, idx: torch.Tensor, epoch: int) -> torch.Tensor:
+        """Bank rows of images ``idx`` in ``epoch`` (1-based): every image uses view (epoch − 1) mod V."""
+        v = (epoch - 1) % self.views
+        return idx if v == 0 else idx + v * self.n
+
+    def epoch_view(self, epoch: int):
+        """(feats [N, K], labels [N]) of ``epoch``'s view: slices of the bank, so the sampler's own
+        image indices are its rows and a training step launches nothing to translate them."""
+        v = (epoch - 1) % self.views
+        return self.feats[v * self.n:(v + 1) * self.n], self.labels[v * self.n:(v + 1) * self.n]
+
+    @staticmethod
+    def nbytes(rows: int, feat_dim: int) -> int:
+        """Bytes of a bank of ``rows`` rows: fp32 features + int64 labels."""
+        return rows * (feat_dim * 4 + 8)
 
 
 GEMMS = ("fma", "mfma")
