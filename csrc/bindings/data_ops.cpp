@@ -129,9 +129,45 @@ torch::Tensor gpu_eval_crop(torch::Tensor data, torch::Tensor idx, int64_t S, in
   return out;
 }
 
+// Mixup (mode 1) / CutMix (mode 2) of an augmented batch x [B][H][W][8] bf16 with its roll(1, 0)
+// (mix.hip), out of place. One lam and one box [y0, y1) x [x0, x1) per call, by value. `out`
+// (optional): the destination, x's shape and dtype, not overlapping x. Everything is checked
+// before the launch: a refused call writes nothing.
+torch::Tensor mix_views(torch::Tensor x, int64_t mode, double lam, int64_t y0, int64_t y1, int64_t x0, int64_t x1,
+                        c10::optional<torch::Tensor> out) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16, "mix_views: x must be a bf16 GPU tensor");
+  TORCH_CHECK(x.dim() == 4 && x.size(3) == 8, "mix_views: x must be [B, H, W, 8]");
+  TORCH_CHECK(x.is_contiguous(), "mix_views: x must be contiguous");
+  const int64_t B = x.size(0), H = x.size(1), W = x.size(2);
+  TORCH_CHECK(B >= 1 && H >= 1 && W >= 1, "mix_views: empty batch");
+  TORCH_CHECK(B * H * W < (1LL << 31), "mix_views: B·H·W must be below 2^31");
+  TORCH_CHECK(mode == kMixMixup || mode == kMixCutmix, "mix_views: mode 1 (mixup) or 2 (cutmix), got ", mode);
+  TORCH_CHECK(lam >= 0.0 && lam <= 1.0, "mix_views: lam must be in [0, 1], got ", lam);
+  if (mode == kMixCutmix) {
+    TORCH_CHECK(0 <= y0 && y0 <= y1 && y1 <= H && 0 <= x0 && x0 <= x1 && x1 <= W, "mix_views: box [", y0, ", ", y1,
+                ") x [", x0, ", ", x1, ") leaves the ", H, " x ", W, " image");
+  } else {
+    y0 = y1 = x0 = x1 = 0;   // (unused)
+  }
+  if (out.has_value()) {
+    TORCH_CHECK(out->is_cuda() && out->get_device() == x.get_device() && out->scalar_type() == at::kBFloat16 &&
+                    out->is_contiguous() && out->sizes() == x.sizes(),
+                "mix_views: out must be a contiguous bf16 tensor of x's shape on x's device");
+  }
+  c10::DeviceGuard dg(x.device());
+  auto o = out.has_value() ? *out : torch::empty_like(x);
+  check_hip(launch_mix_views(x.data_ptr(), o.data_ptr(), (int)B, (int)H, (int)W, (int)mode, (float)lam, (int)y0,
+                             (int)y1, (int)x0, (int)x1, cur_stream()),
+            "mix_views");
+  return o;
+}
+
 }  // namespace
 
 void register_data(pybind11::module& m) {
+  m.def("mix_views", &mix_views, "Mixup (mode 1) / CutMix (mode 2) of a [B, H, W, 8] bf16 batch with its roll(1, 0)",
+        pybind11::arg("x"), pybind11::arg("mode"), pybind11::arg("lam"), pybind11::arg("y0"), pybind11::arg("y1"),
+        pybind11::arg("x0"), pybind11::arg("x1"), pybind11::arg("out") = pybind11::none());
   m.def("gpu_augment", &gpu_augment, "fused SimCLR augmentation -> NHWC bf16 (C padded to 8)",
         pybind11::arg("data"), pybind11::arg("idx"), pybind11::arg("S"), pybind11::arg("n_views"),
         pybind11::arg("seed"), pybind11::arg("mean"), pybind11::arg("std"), pybind11::arg("scale_lo"),

@@ -235,6 +235,43 @@ std::vector<torch::Tensor> ce_head_fwd(torch::Tensor x, torch::Tensor W, torch::
   return {logits, dz, rowstat, stats, loss};
 }
 
+// the second label vector and the scalars of the soft-target ops (Mixup / CutMix / label smoothing)
+void check_soft(const char* op, const torch::Tensor& labels2, int64_t B, int dev, double lam, double eps) {
+  TORCH_CHECK(labels2.is_cuda() && labels2.scalar_type() == at::kLong && labels2.numel() == B &&
+                  labels2.is_contiguous() && labels2.get_device() == dev,
+              op, ": labels2: int64 [B] on x's device");
+  TORCH_CHECK(lam >= 0.0 && lam <= 1.0, op, ": lam must be in [0, 1], got ", lam);
+  TORCH_CHECK(eps >= 0.0 && (float)eps < 1.f, op, ": eps must be in [0, 1), got ", eps);
+}
+
+// ce_head_fwd with the soft target t_c = (1 − eps)·(lam·[c = labels] + (1 − lam)·[c = labels2]) + eps / C:
+// the same outputs, hits counted against `labels`; the backward op is ce_head_bwd, unchanged.
+// labels2 = labels, lam = 1, eps = 0 is bit-identical to ce_head_fwd.
+std::vector<torch::Tensor> ce_head_fwd_soft(torch::Tensor x, torch::Tensor W, torch::Tensor b, torch::Tensor labels,
+                                            torch::Tensor labels2, double lam, double eps, bool reduce) {
+  check_classifier(x, W, b, labels);
+  const int64_t B = x.size(0), K = x.size(1), C = W.size(0);
+  check_soft("ce_head_fwd_soft", labels2, B, x.get_device(), lam, eps);
+  c10::DeviceGuard dg(x.device());
+  auto fo = x.options();
+  auto logits = torch::empty({B, C}, fo);
+  auto dz = torch::empty({B, C}, fo);
+  auto rowstat = torch::empty({B, 3}, fo);
+  auto stats = torch::empty({3}, fo);
+  auto loss = torch::empty({}, fo);
+  check_hip(launch_linear_ce_fwd_soft(x.data_ptr<float>(), W.data_ptr<float>(), b.data_ptr<float>(),
+                                      labels.data_ptr<int64_t>(), labels2.data_ptr<int64_t>(), (float)lam, (float)eps,
+                                      (int)B, (int)K, (int)C, (float)(1.0 / B), logits.data_ptr<float>(),
+                                      dz.data_ptr<float>(), rowstat.data_ptr<float>(), cur_stream()),
+            "ce_head_fwd_soft");
+  if (reduce)
+    check_hip(launch_ce_head_bwd(nullptr, nullptr, nullptr, (int)B, (int)K, (int)C, nullptr, nullptr, nullptr, nullptr,
+                                 rowstat.data_ptr<float>(), stats.data_ptr<float>(), loss.data_ptr<float>(),
+                                 cur_stream()),
+              "ce_head_stats");
+  return {logits, dz, rowstat, stats, loss};
+}
+
 // Training form, backward (one launch): returns dX [B][K] = gout·dz·W (need_dx), accumulates
 // dW += gout·dzᵀ·x and db += gout·Σ_b dz into the given destinations (contiguous fp32, views of
 // a larger buffer allowed) and writes stats / loss from rowstat. gout: scalar fp32 GPU tensor.
@@ -415,6 +452,38 @@ std::vector<torch::Tensor> ce_head_fwd_mfma(torch::Tensor x, torch::Tensor W, to
   return {logits, dz, rowstat, stats, loss};
 }
 
+// ce_head_fwd_soft on the MFMA logits GEMM: bit-identical to ce_head_fwd_mfma for labels2 = labels,
+// lam = 1, eps = 0; the backward op is ce_head_bwd_mfma, unchanged
+std::vector<torch::Tensor> ce_head_fwd_soft_mfma(torch::Tensor x, torch::Tensor W, torch::Tensor b,
+                                                 torch::Tensor labels, torch::Tensor labels2, double lam, double eps,
+                                                 bool reduce) {
+  const char* op = "ce_head_fwd_soft_mfma";
+  check_head_gemm_classifier(op, x, W);
+  const int64_t B = x.size(0), K = x.size(1), C = W.size(0);
+  check_f32(b, {C}, "b");
+  TORCH_CHECK(b.get_device() == x.get_device(), op, ": one device");
+  check_labels(labels, B, x.get_device());
+  check_soft(op, labels2, B, x.get_device(), lam, eps);
+  c10::DeviceGuard dg(x.device());
+  auto fo = x.options();
+  auto logits = torch::empty({B, C}, fo);
+  auto dz = torch::empty({B, C}, fo);
+  auto rowstat = torch::empty({B, 3}, fo);
+  auto stats = torch::empty({3}, fo);
+  auto loss = torch::empty({}, fo);
+  check_hip(launch_head_gemm_logits_soft(x.data_ptr<float>(), W.data_ptr<float>(), b.data_ptr<float>(),
+                                         labels.data_ptr<int64_t>(), labels2.data_ptr<int64_t>(), (float)lam,
+                                         (float)eps, (int)B, (int)K, (int)C, (float)(1.0 / B),
+                                         logits.data_ptr<float>(), dz.data_ptr<float>(), rowstat.data_ptr<float>(),
+                                         cur_stream()),
+            op);
+  if (reduce)
+    check_hip(launch_head_gemm_stats(1, (int)B, (int)K, (int)C, rowstat.data_ptr<float>(), stats.data_ptr<float>(),
+                                     loss.data_ptr<float>(), cur_stream()),
+              op);
+  return {logits, dz, rowstat, stats, loss};
+}
+
 c10::optional<torch::Tensor> ce_head_bwd_mfma(torch::Tensor x, torch::Tensor dz, torch::Tensor W, torch::Tensor gout,
                                               torch::Tensor rowstat, torch::Tensor stats, torch::Tensor loss, OptT dW,
                                               OptT db, bool need_dx) {
@@ -477,6 +546,13 @@ void register_probe(pybind11::module& m) {
         pybind11::arg("first"), pybind11::arg("train"));
   m.def("ce_head_fwd_mfma", &ce_head_fwd_mfma, "ce_head_fwd on bf16x3 MFMA GEMMs", pybind11::arg("x"),
         pybind11::arg("W"), pybind11::arg("b"), pybind11::arg("labels"), pybind11::arg("reduce"));
+  m.def("ce_head_fwd_soft", &ce_head_fwd_soft,
+        "ce_head_fwd with a two-label, label-smoothed target (Mixup / CutMix / label smoothing)", pybind11::arg("x"),
+        pybind11::arg("W"), pybind11::arg("b"), pybind11::arg("labels"), pybind11::arg("labels2"),
+        pybind11::arg("lam"), pybind11::arg("eps"), pybind11::arg("reduce"));
+  m.def("ce_head_fwd_soft_mfma", &ce_head_fwd_soft_mfma, "ce_head_fwd_soft on the bf16x3 MFMA logits GEMM",
+        pybind11::arg("x"), pybind11::arg("W"), pybind11::arg("b"), pybind11::arg("labels"),
+        pybind11::arg("labels2"), pybind11::arg("lam"), pybind11::arg("eps"), pybind11::arg("reduce"));
   m.def("ce_head_bwd_mfma", &ce_head_bwd_mfma, "ce_head_bwd on bf16x3 MFMA GEMMs", pybind11::arg("x"),
         pybind11::arg("dz"), pybind11::arg("W"), pybind11::arg("gout"), pybind11::arg("rowstat"),
         pybind11::arg("stats"), pybind11::arg("loss"), pybind11::arg("dW"), pybind11::arg("db"),

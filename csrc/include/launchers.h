@@ -29,6 +29,12 @@ bool linear_ce_supported(int K, int C);
 hipError_t launch_linear_ce_fwd(const float* x, const float* W, const float* bias, const int64_t* labels, int B,
                                 int K, int C, float gscale, float* logits, float* dz, float* rowstat, hipStream_t s,
                                 const int64_t* rows = nullptr, long N = 0);
+// The SOFT form (soft_ce.h; plain rows only): two labels per row, target t_c = (1 − eps)·(lam·[c = a]
+// + (1 − lam)·[c = b]) + eps / C, hits against `labels`; 0 <= lam <= 1, 0 <= eps < 1.
+// labels2 = labels, lam = 1, eps = 0 is bit-identical to launch_linear_ce_fwd
+hipError_t launch_linear_ce_fwd_soft(const float* x, const float* W, const float* bias, const int64_t* labels,
+                                     const int64_t* labels2, float lam, float eps, int B, int K, int C, float gscale,
+                                     float* logits, float* dz, float* rowstat, hipStream_t s);
 // probe form: gradient + SGD update of (W, b) in place, stats[3] = Σ_rows rowstat
 hipError_t launch_linear_ce_sgd(const float* x, const float* dz, int B, int K, int C, float* W, float* bias,
                                 float* bufW, float* bufb, float lr, float mom, float wd, int first,
@@ -53,6 +59,11 @@ bool head_gemm_supported(int G, int B, int K, int C);
 hipError_t launch_head_gemm_logits(const float* x, const float* W, const float* bias, const int64_t* labels, int G,
                                    int B, int K, int C, float gscale, float* logits, float* dz, float* rowstat,
                                    hipStream_t s, const int64_t* rows = nullptr, long N = 0);
+// The SOFT form for one head (G = 1, plain rows), as launch_linear_ce_fwd_soft: the same logits
+// GEMM, then the soft row kernel; labels2 = labels, lam = 1, eps = 0 is bit-identical to the above
+hipError_t launch_head_gemm_logits_soft(const float* x, const float* W, const float* bias, const int64_t* labels,
+                                        const int64_t* labels2, float lam, float eps, int B, int K, int C,
+                                        float gscale, float* logits, float* dz, float* rowstat, hipStream_t s);
 // 1 launch: stats [G][3] = Σ_rows rowstat (fp64, row order); loss (optional, G = 1) = stats[0] / B
 hipError_t launch_head_gemm_stats(int G, int B, int K, int C, const float* rowstat, float* stats, float* loss,
                                   hipStream_t s);
@@ -322,6 +333,16 @@ hipError_t launch_gpu_augment_blur(const uint8_t* data, const int64_t* idx, int 
 hipError_t launch_gpu_eval_crop(const uint8_t* data, const int64_t* idx, int B, int H, int W, int S, int R,
                                 const float* mean, const float* std, void* out, hipStream_t s, long n_data = 0,
                                 const int64_t* offs = nullptr, const int32_t* hw = nullptr);
+
+// ---- Mixup / CutMix of an augmented batch (mix.hip) -----------------------------
+enum MixMode { kMixMixup = 1, kMixCutmix = 2 };
+// x, out [B][H][W][8] bf16, 16-byte aligned, not overlapping; the partner of image i is image
+// (i − 1) mod B. kMixCutmix: the partner's pixels inside [y0, y1) x [x0, x1), bit copies;
+// kMixMixup: bf16(lam·x[i] + (1 − lam)·x[i−1]), fp32 products and sum, one bf16 rounding.
+// hipErrorInvalidValue before any launch for an empty batch, B·H·W >= 2^31, another mode, lam
+// outside [0, 1] or a box that leaves the image.
+hipError_t launch_mix_views(const void* x, void* out, int B, int H, int W, int mode, float lam, int y0, int y1, int x0,
+                            int x1, hipStream_t s);
 
 // ---- optimizers (optim.hip) -----------------------------------------------------
 hipError_t launch_sgd(float* p, const float* g, float* buf, long n, const float* lr, float momentum, float wd,

@@ -47,6 +47,7 @@
 #include "common.h"
 #include "head_gemm_plan.h"
 #include "launchers.h"
+#include "soft_ce.h"
 
 using namespace sdx;
 
@@ -371,6 +372,23 @@ __global__ __launch_bounds__(256) void ce_rows_kernel(const float* __restrict__ 
   }
 }
 
+// The SOFT form of ce_rows_kernel<false> for one head (Mixup / CutMix / label smoothing): rows = B
+// logits rows, two labels per row and the target weights of soft_ce.h; the logits stay where the
+// GEMM wrote them
+__global__ __launch_bounds__(256) void ce_rows_soft_kernel(const float* __restrict__ logits,
+                                                           const int64_t* __restrict__ labels,
+                                                           const int64_t* __restrict__ labels2, SoftTarget t, int B,
+                                                           int C, float gscale, float* __restrict__ dz,
+                                                           float* __restrict__ rowstat) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * hg::kRowsPerBlock + (threadIdx.x >> 6);
+  if (row >= B) return;
+  const int64_t la = labels[row], lb = labels2[row];
+  const bool ok = la >= 0 && la < C && lb >= 0 && lb < C;
+  soft_ce_row(logits + (size_t)row * C, C, ok ? (int)la : -1, ok ? (int)lb : -1, ok, t, gscale, nullptr,
+              dz != nullptr ? dz + (size_t)row * C : nullptr, rowstat + (size_t)row * 3, lane);
+}
+
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 Operand operand(const float* p, int lim_i, int lim_r, long si, long sr, int hc = INT_MAX, long hs = 0) {
@@ -420,6 +438,34 @@ hipError_t launch_head_gemm_logits(const float* x, const float* W, const float* 
     hipLaunchKernelGGL((head_gemm_kernel<kRowScalar, kVec, kLogits, kMapOut>), grid, blk, 0, s, p, rm);
   SDX_LAUNCH_CHECK();
   hipLaunchKernelGGL(ce_rows_kernel<true>, rgrid, blk, 0, s, logits, labels, rm, pl.rows, B, C, gscale, dz, rowstat);
+  SDX_LAUNCH_CHECK();
+  return hipSuccess;
+}
+
+hipError_t launch_head_gemm_logits_soft(const float* x, const float* W, const float* bias, const int64_t* labels,
+                                        const int64_t* labels2, float lam, float eps, int B, int K, int C,
+                                        float gscale, float* logits, float* dz, float* rowstat, hipStream_t s) {
+  hg::Plan pl;
+  if (!hg::make_plan(1, B, K, C, &pl)) return hipErrorInvalidValue;
+  if (x == nullptr || W == nullptr || bias == nullptr || labels == nullptr || labels2 == nullptr ||
+      logits == nullptr || rowstat == nullptr)
+    return hipErrorInvalidValue;
+  if (!aligned16(x) || !aligned16(W) || !aligned16(logits) || (dz != nullptr && !aligned16(dz)))
+    return hipErrorInvalidValue;
+  if (!(lam >= 0.f && lam <= 1.f) || !(eps >= 0.f && eps < 1.f)) return hipErrorInvalidValue;
+  GemmParams p = {};
+  p.a = operand(x, B, K, K, 1);
+  p.b = operand(W, C, K, K, 1);
+  set_form(p, pl.nt);
+  p.G = 1; p.B = B; p.C = C; p.K = K;
+  p.out = logits;
+  p.bias = bias;
+  // the plain launcher's logits GEMM, then the soft row kernel
+  hipLaunchKernelGGL((head_gemm_kernel<kVec, kVec, kLogits>), dim3(pl.nt.tiles), dim3(256), 0, s, p,
+                     RowMap{nullptr, 0});
+  SDX_LAUNCH_CHECK();
+  hipLaunchKernelGGL(ce_rows_soft_kernel, dim3(pl.row_blocks), dim3(256), 0, s, logits, labels, labels2,
+                     make_soft_target(lam, eps, C), B, C, gscale, dz, rowstat);
   SDX_LAUNCH_CHECK();
   return hipSuccess;
 }

@@ -18,7 +18,9 @@ Additions (new flags only; no reference flag changes meaning):
 ``--val_folder`` / ``--resize`` (ImageFolder evaluation: Resize + CenterCrop on the GPU; the linear
 probe also takes ``--dataset path`` with ``--size`` / ``--mean`` / ``--std``),
 ``--sweep_lr`` / ``--sweep_wd`` (linear probe: one classifier per (lr, wd) pair on one encoder pass),
-``--cache_features`` / ``--cache_views`` (linear probe: encode the frozen encoder's features once).
+``--cache_features`` / ``--cache_views`` (linear probe: encode the frozen encoder's features once),
+``--label_smoothing`` / ``--mixup`` / ``--cutmix`` / ``--mix_prob`` / ``--mix_switch_prob`` (supervised
+trainer: soft-target regularisers, data/augment.py ``mix_draw``).
 Fixes: ``--num_workers`` is honoured (Q6): it sizes the image-decode thread pool of
 ``dataset=path`` and the CPU augmentation threads of ``--gpu_aug 0`` (the default pipeline
 is the GPU kernel, which needs no workers); ``dataset=path`` parses ``--mean/--std``
@@ -348,6 +350,59 @@ class _HeadOptions(argparse.Namespace):
     cache_views = 0
 
 
+class _CeOptions(_HeadOptions):
+    """The supervised trainer's soft-target flags, absent from ``vars(opt)`` when not given."""
+    label_smoothing = 0.0
+    mixup = 0.0
+    cutmix = 0.0
+    mix_prob = 1.0
+    mix_switch_prob = 0.5
+
+
+def _add_mix_flags(g):
+    S = argparse.SUPPRESS
+    g.add_argument("--label_smoothing", type=float, default=S, metavar="E",
+                   help="label smoothing: the target is (1 - E) x the label distribution + E / n_cls; 0 <= E < 1, "
+                        "default 0")
+    g.add_argument("--mixup", type=float, default=S, metavar="A",
+                   help="Mixup: blend every image with its batch neighbour, lambda ~ Beta(A, A) per step; default 0 = off")
+    g.add_argument("--cutmix", type=float, default=S, metavar="A",
+                   help="CutMix: paste a box of the batch neighbour, box area 1 - lambda, lambda ~ Beta(A, A) per step; "
+                        "default 0 = off")
+    g.add_argument("--mix_prob", type=float, default=S, metavar="P",
+                   help="probability that a step mixes at all (with --mixup / --cutmix); default 1")
+    g.add_argument("--mix_switch_prob", type=float, default=S, metavar="Q",
+                   help="with both --mixup and --cutmix: probability that a mixing step uses CutMix; default 0.5")
+
+
+def _check_mix_flags(parser, opt):
+    """Ranges of the soft-target flags (a parser error outside them) and the model_name suffix of
+    those in effect."""
+    if not 0.0 <= opt.label_smoothing < 1.0:
+        parser.error(f"--label_smoothing {opt.label_smoothing} must be in [0, 1)")
+    for name in ("mixup", "cutmix"):
+        a = getattr(opt, name)
+        if not (0.0 <= a < math.inf):
+            parser.error(f"--{name} {a}: the Beta parameter must be finite and >= 0 (0 = off)")
+    for name in ("mix_prob", "mix_switch_prob"):
+        v = getattr(opt, name)
+        if not 0.0 <= v <= 1.0:
+            parser.error(f"--{name} {v} must be in [0, 1]")
+    suffix = ""
+    if opt.label_smoothing > 0:
+        suffix += f"_ls_{opt.label_smoothing}"
+    if opt.mixup > 0:
+        suffix += f"_mixup_{opt.mixup}"
+    if opt.cutmix > 0:
+        suffix += f"_cutmix_{opt.cutmix}"
+    if opt.mixup > 0 or opt.cutmix > 0:
+        if opt.mix_prob != 1.0:
+            suffix += f"_mixp_{opt.mix_prob}"
+        if opt.mixup > 0 and opt.cutmix > 0 and opt.mix_switch_prob != 0.5:
+            suffix += f"_switch_{opt.mix_switch_prob}"
+    return suffix
+
+
 def _add_head_gemm_flag(g):
     g.add_argument("--head_gemm", type=str, default=argparse.SUPPRESS, choices=["fma", "mfma"],
                    help="classifier GEMMs: fma = the fp32 kernels (K = 64·2^j <= 2048, C <= 1024), mfma = split-bf16 "
@@ -488,13 +543,16 @@ def ce_parser() -> argparse.ArgumentParser:
     g.add_argument("--blur_sigma", type=float, nargs=2, default=[0.1, 2.0], metavar=("LO", "HI"))
     _add_eval_flags(g)
     _add_head_gemm_flag(g)
+    _add_mix_flags(g)
     _add_common_new_flags(p)
     return p
 
 
 def parse_ce(argv: Optional[Sequence[str]] = None, make_dirs: bool = True,
              now: Optional[datetime.datetime] = None):
-    opt = ce_parser().parse_args(argv, namespace=_HeadOptions())
+    parser = ce_parser()
+    opt = parser.parse_args(argv, namespace=_CeOptions())
+    mix_suffix = _check_mix_flags(parser, opt)
     if opt.cuda_graph or opt.micro_batch:
         raise ValueError("main_ce.py supports neither --cuda_graph nor --micro_batch")
     if not 0.0 < opt.label_frac <= 1.0:
@@ -522,6 +580,7 @@ def parse_ce(argv: Optional[Sequence[str]] = None, make_dirs: bool = True,
         opt.dataset, opt.model, opt.learning_rate, opt.weight_decay, opt.batch_size, opt.trial)
     if opt.label_frac < 1.0:
         opt.model_name = f"{opt.model_name}_frac_{opt.label_frac}"
+    opt.model_name += mix_suffix
     if opt.cosine:
         opt.model_name = f"{opt.model_name}_cosine"
     if opt.batch_size > 256:

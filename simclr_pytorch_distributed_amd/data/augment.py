@@ -399,6 +399,78 @@ def augment(data: torch.Tensor, idx: torch.Tensor, cfg: AugConfig, seed: int, of
     return augment_reference(data, idx, cfg, seed, offs, hw)
 
 
+# ---- Mixup / CutMix of an augmented batch (supervised trainer) ------------------------------
+MIX_NONE, MIX_MIXUP, MIX_CUTMIX = "none", "mixup", "cutmix"
+_MIX_MODE_ID = {MIX_MIXUP: 1, MIX_CUTMIX: 2}       # csrc/include/launchers.h MixMode
+# xor-ed into the step seed: the mixing draws share no stream with the augmentation's
+_MIX_STREAM = 0x6D69785F64726177
+
+
+def cutmix_box(lam: float, cy: int, cx: int, S: int):
+    """torchvision v2 ``CutMix`` on an S x S image: the box (y0, y1, x0, x1) of half-side
+    int(0.5·sqrt(1 − λ)·S) around the centre (cy, cx), clipped to the image, and λ replaced by
+    1 − box_area / S²."""
+    half = int(0.5 * math.sqrt(1.0 - lam) * S)
+    y0, x0 = max(cy - half, 0), max(cx - half, 0)
+    y1, x1 = min(cy + half, S), min(cx + half, S)
+    return (y0, y1, x0, x1), 1.0 - (y1 - y0) * (x1 - x0) / (S * S)
+
+
+def mix_draw(opt, seed: int, epoch: int, it: int, rank: int):
+    """``(mode, lam, box)`` of one step of one rank: ``mode`` in {none, mixup, cutmix}, one
+    λ ~ Beta(α, α) and one box ``(y0, y1, x0, x1)`` for the whole batch (batch mode, as torchvision
+    v2 and timm's default). ``opt`` supplies ``mixup`` / ``cutmix`` (the α, 0 = off), ``mix_prob``,
+    ``mix_switch_prob`` and ``size``. Host-only and a function of (seed, epoch, it, rank) alone: a
+    resumed run draws what the uninterrupted one drew."""
+    a_mix, a_cut = float(getattr(opt, "mixup", 0.0)), float(getattr(opt, "cutmix", 0.0))
+    none = (MIX_NONE, 1.0, (0, 0, 0, 0))
+    if a_mix <= 0 and a_cut <= 0:
+        return none
+    from ..engine.base import step_seed
+    rng = np.random.default_rng(step_seed(seed, epoch, it, rank) ^ _MIX_STREAM)
+    # every draw is made whatever the earlier ones decide: one layout of the stream
+    u_mix, u_switch = rng.random(), rng.random()
+    cut = a_cut > 0 and (a_mix <= 0 or u_switch < float(getattr(opt, "mix_switch_prob", 0.5)))
+    alpha = a_cut if cut else a_mix
+    lam = float(rng.beta(alpha, alpha))
+    S = int(opt.size)
+    cy, cx = int(rng.integers(S)), int(rng.integers(S))
+    if not u_mix < float(getattr(opt, "mix_prob", 1.0)):
+        return none
+    if not cut:
+        return MIX_MIXUP, lam, (0, 0, 0, 0)
+    box, lam = cutmix_box(lam, cy, cx, S)
+    return MIX_CUTMIX, lam, box
+
+
+def mix_views(x: torch.Tensor, mode: str, lam: float, y0: int = 0, y1: int = 0, x0: int = 0, x1: int = 0,
+              out=None) -> torch.Tensor:
+    """The mixing kernel (csrc/kernels/mix.hip) on a [B, S, S, 8] bf16 batch: image i with image
+    (i − 1) mod B, out of place. Mixup: bf16(λ·x[i] + (1 − λ)·x[i−1]); CutMix: x[i−1] inside
+    [y0, y1) x [x0, x1), bit for bit."""
+    return _ext.require().mix_views(x, _MIX_MODE_ID[mode], float(lam), y0, y1, x0, x1, out)
+
+
+def mix_reference(x: torch.Tensor, mode: str, lam: float, box=(0, 0, 0, 0), layout: str = "nchw") -> torch.Tensor:
+    """The fp32 torch twin of :func:`mix_views` (torch backend, CPU, ``--gpu_aug 0``): ``x`` is
+    [B, C, H, W] (``layout="nchw"``) or [B, H, W, C]; λ and 1 − λ are taken in fp32 as the kernel
+    takes them, and the result has x's dtype (one rounding)."""
+    xr = x.roll(1, 0)
+    if mode == MIX_CUTMIX:
+        y0, y1, x0, x1 = box
+        out = x.clone()
+        if layout == "nchw":
+            out[:, :, y0:y1, x0:x1] = xr[:, :, y0:y1, x0:x1]
+        else:
+            out[:, y0:y1, x0:x1, :] = xr[:, y0:y1, x0:x1, :]
+        return out
+    if mode != MIX_MIXUP:
+        raise ValueError(f"mix mode {mode!r}")
+    w0 = np.float32(lam)
+    w1 = np.float32(1.0) - w0
+    return (float(w0) * x.float() + float(w1) * xr.float()).to(x.dtype)
+
+
 def nhwc8_to_nchw(x: torch.Tensor) -> torch.Tensor:
     """NHWC [.., 8] -> NCHW float [.., 3, H, W] for the torch backend."""
     return x[..., :3].permute(0, 3, 1, 2).float().contiguous()

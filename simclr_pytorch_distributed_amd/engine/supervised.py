@@ -32,6 +32,7 @@ import time
 import numpy as np
 import torch
 
+from ..data import augment as aug_mod
 from ..data.augment import AugConfig
 from ..data.sampler import DistributedIndexSampler, label_subset
 from ..data.store import probe_stores
@@ -105,6 +106,18 @@ class SupervisedEngine(TrainEngine):
         self._syncbn_pending = False      # (no transport measurement in this trainer)
         self.history = []          # one dict per finished epoch (train / validation figures)
         self._head_gemm = None     # decided at the first step, when the model sits on its device
+        opt = self.opt
+        self.smoothing = float(getattr(opt, "label_smoothing", 0.0))
+        self.mixing = getattr(opt, "mixup", 0.0) > 0 or getattr(opt, "cutmix", 0.0) > 0
+        if self.mixing or self.smoothing > 0:
+            on = [f"{k} {getattr(opt, k)}" for k in ("mixup", "cutmix") if getattr(opt, k, 0.0) > 0]
+            if self.mixing:
+                on.append(f"mix_prob {getattr(opt, 'mix_prob', 1.0)}")
+            if len(on) == 3:
+                on.append(f"mix_switch_prob {getattr(opt, 'mix_switch_prob', 0.5)}")
+            if self.smoothing > 0:
+                on.append(f"label_smoothing {self.smoothing}")
+            logging.info("soft targets: " + ", ".join(on) + " (train Acc@1 counts the dominant label)")
 
     def head_gemm(self) -> str:
         """--head_gemm where it can run; else the default path, with one warning line."""
@@ -128,13 +141,37 @@ class SupervisedEngine(TrainEngine):
         ph = self.prof.phase
         with ph("augment"):
             zeroed, x = self._start_step(idx, epoch, it)
+        soft = {}
+        if self.mixing or self.smoothing > 0:
+            x, soft = self._mix(x, labels, epoch, it)
+            labels = soft.pop("labels")
         with ph("forward"):
             feat = self.runner.encode(x)
         with ph("loss"):
             loss, stats = classifier_ce(feat, self.model.fc, labels, native=self.backend == "native",
-                                        gemm=self.head_gemm())
+                                        gemm=self.head_gemm(), **soft)
         self._backward_and_update(loss, zeroed)
         return {"loss_local": loss.detach(), "stats": stats}
+
+    def _mix(self, x: torch.Tensor, labels: torch.Tensor, epoch: int, it: int):
+        """Mixup / CutMix of the step's views by the host draw of ``mix_draw`` (one λ and one box
+        per step, by value: no device random numbers, no synchronisation) and the soft-target
+        arguments of ``classifier_ce``. The partner of row i is row i − 1; ``labels`` comes back as
+        the label that weighs at least one half."""
+        mode, lam, box = aug_mod.mix_draw(self.opt, self.opt.seed, epoch, it, self.rank)
+        soft = {"labels": labels, "smoothing": self.smoothing}
+        if mode == aug_mod.MIX_NONE:
+            return x, soft
+        with self.prof.phase("mix"):
+            if self.backend == "native" and getattr(self.opt, "gpu_aug", 1):
+                x = aug_mod.mix_views(x, mode, lam, *box)
+            else:
+                x = aug_mod.mix_reference(x, mode, lam, box, "nhwc" if self.backend == "native" else "nchw")
+        labels2 = labels.roll(1)
+        if lam < 0.5:
+            labels, labels2, lam = labels2, labels, 1.0 - lam
+        soft.update(labels=labels, labels2=labels2, lam=lam)
+        return x, soft
 
     def train_step(self, idx: torch.Tensor, labels: torch.Tensor, epoch: int, it: int, iters: int):
         return self._train_step((idx, labels), epoch, it, iters)

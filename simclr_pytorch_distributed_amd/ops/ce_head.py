@@ -22,6 +22,12 @@ Unsupported shapes (K ≠ 64·2^j, K > 2048, C > 1024), CPU tensors and the ``to
 kernels (csrc/kernels/head_gemm.hip) for any K = 64·j <= 4096 and C <= 32768: two launches
 forward, two backward, the same outputs, sinks and statistics convention. The default stays
 ``fma``.
+
+Soft targets (``labels2`` / ``lam`` / ``smoothing``: Mixup, CutMix, label smoothing): the target of
+a row with labels a, b is t_c = (1 − ε)·(λ·[c = a] + (1 − λ)·[c = b]) + ε/C. Only the forward's row
+softmax changes (``ce_head_fwd_soft[_mfma]``: loss = lse − Σ_c t_c·z_c, dz = (softmax − t) / B, hits
+against a); the backward launches read dz and are the same ops. With the defaults the node is the
+plain one, launch for launch.
 """
 from __future__ import annotations
 
@@ -45,14 +51,19 @@ def supported(fc: torch.nn.Linear, gemm: str = "fma") -> bool:
 
 class _ClassifierCE(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, feat, labels, fc, record, gemm, *params):
+    def forward(ctx, feat, labels, fc, record, gemm, soft, *params):
         m = _ext.require()
-        fwd = m.ce_head_fwd_mfma if gemm == "mfma" else m.ce_head_fwd
         x = feat.detach().float().contiguous()
         w = fc.weight.detach()
         # record: a backward will follow (decided by the caller: grad mode is off in here)
-        need = [ctx.needs_input_grad[0], any(ctx.needs_input_grad[5:])]
-        logits, dz, rowstat, stats, loss = fwd(x, w, fc.bias.detach(), labels, not record)
+        need = [ctx.needs_input_grad[0], any(ctx.needs_input_grad[6:])]
+        if soft is None:
+            fwd = m.ce_head_fwd_mfma if gemm == "mfma" else m.ce_head_fwd
+            logits, dz, rowstat, stats, loss = fwd(x, w, fc.bias.detach(), labels, not record)
+        else:
+            labels2, lam, eps = soft
+            fwd = m.ce_head_fwd_soft_mfma if gemm == "mfma" else m.ce_head_fwd_soft
+            logits, dz, rowstat, stats, loss = fwd(x, w, fc.bias.detach(), labels, labels2, lam, eps, not record)
         ctx.save_for_backward(x, dz, w, rowstat, stats, loss)
         ctx.fc = fc
         ctx.gemm = gemm
@@ -75,24 +86,46 @@ class _ClassifierCE(torch.autograd.Function):
                  t(fc.weight) if need_dw else None, t(fc.bias) if need_dw else None, need_dx)
         if need_dw:
             sinks.notify(ctx.params)
-        return (dx.to(ctx.feat_dtype) if dx is not None else None, None, None, None, None) + (None,) * len(ctx.params)
+        return (dx.to(ctx.feat_dtype) if dx is not None else None,) + (None,) * (5 + len(ctx.params))
+
+
+def soft_target(labels: torch.Tensor, labels2: torch.Tensor, lam: float, smoothing: float, n_cls: int,
+                dtype=torch.float32) -> torch.Tensor:
+    """The probability target [B, C]: t_c = (1 − ε)·(λ·[c = a] + (1 − λ)·[c = b]) + ε/C."""
+    a = F.one_hot(labels.long(), n_cls).to(dtype)
+    b = F.one_hot(labels2.long(), n_cls).to(dtype)
+    return (1.0 - smoothing) * (lam * a + (1.0 - lam) * b) + smoothing / n_cls
 
 
 def classifier_ce_logits(feat: torch.Tensor, fc: torch.nn.Linear, labels: torch.Tensor,
-                         native: bool = True, gemm: str = "fma") -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+                         native: bool = True, gemm: str = "fma", labels2=None, lam: float = 1.0,
+                         smoothing: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """(loss, stats, logits) of ``F.cross_entropy(fc(feat), labels)``: ``loss`` the batch mean,
     ``stats`` = [Σ_rows CE, top-1 hits, top-5 hits] (fp32, no gradient), ``logits`` [B, C] (no
     gradient). ``native=False`` forces the torch ops. ``gemm="mfma"``: the GEMMs of the node on
     csrc/kernels/head_gemm.hip; a classifier outside its range is an error here (the engines decide
-    beforehand, with one warning, which path a run takes)."""
+    beforehand, with one warning, which path a run takes).
+
+    ``labels2`` / ``lam`` / ``smoothing``: the soft target of the module docstring (``labels2``
+    None = ``labels``); the loss is then ``F.cross_entropy(logits, t)`` with the probability target
+    and the hits are counted against ``labels``. With the defaults this is the plain path."""
     labels = labels.long()
+    lam, smoothing = float(lam), float(smoothing)
+    if not (0.0 <= lam <= 1.0 and 0.0 <= smoothing < 1.0):
+        raise ValueError(f"lam {lam} must be in [0, 1] and smoothing {smoothing} in [0, 1)")
+    soft = None
+    if labels2 is not None or lam != 1.0 or smoothing != 0.0:
+        soft = ((labels if labels2 is None else labels2.long()).contiguous(), lam, smoothing)
     if native and feat.is_cuda and gemm == "mfma" and not supported(fc, "mfma"):
         raise ValueError(f"gemm='mfma' cannot run a {fc.in_features} x {fc.out_features} classifier")
     if native and feat.is_cuda and supported(fc, gemm):
         record = torch.is_grad_enabled() and (feat.requires_grad or fc.weight.requires_grad or fc.bias.requires_grad)
-        return _ClassifierCE.apply(feat, labels.contiguous(), fc, record, gemm, fc.weight, fc.bias)
+        return _ClassifierCE.apply(feat, labels.contiguous(), fc, record, gemm, soft, fc.weight, fc.bias)
     logits = F.linear(feat.float(), fc.weight, fc.bias)
-    loss = F.cross_entropy(logits, labels)
+    if soft is None:
+        loss = F.cross_entropy(logits, labels)
+    else:
+        loss = F.cross_entropy(logits, soft_target(labels, soft[0], lam, smoothing, fc.out_features, logits.dtype))
     with torch.no_grad():
         z = logits.detach()
         # the kernel's rank rule: a row hits@k when fewer than k logits exceed the label's
@@ -102,7 +135,11 @@ def classifier_ce_logits(feat: torch.Tensor, fc: torch.nn.Linear, labels: torch.
 
 
 def classifier_ce(feat: torch.Tensor, fc: torch.nn.Linear, labels: torch.Tensor,
-                  native: bool = True, gemm: str = "fma") -> Tuple[torch.Tensor, torch.Tensor]:
+                  native: bool = True, gemm: str = "fma", labels2=None, lam: float = 1.0,
+                  smoothing: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor]:
     """``(loss, stats)`` — see :func:`classifier_ce_logits`."""
-    loss, stats, _ = classifier_ce_logits(feat, fc, labels, native, gemm)
+    if labels2 is None and lam == 1.0 and smoothing == 0.0:
+        loss, stats, _ = classifier_ce_logits(feat, fc, labels, native, gemm)      # today's call, as it was
+    else:
+        loss, stats, _ = classifier_ce_logits(feat, fc, labels, native, gemm, labels2, lam, smoothing)
     return loss, stats
