@@ -153,7 +153,9 @@ def test_native_engine_step_emulated_syncbn(gpu, tmp_path, monkeypatch, kind):
 
 
 def test_native_blocks_teacher_forced(gpu):
-    """Each native block vs the torch block fed the same (bf16-rounded) input."""
+    """Each native block vs the torch block fed the same (bf16-rounded) input. A norm envelope
+    at ResNet shapes; the strict, stage-wise check of the executor is
+    tests/test_gpu_block_oracle.py."""
     from simclr_pytorch_distributed_amd.models import executor as ex
     from simclr_pytorch_distributed_amd.models.resnet import SupConResNet
     torch.manual_seed(0)
@@ -174,7 +176,8 @@ def test_native_blocks_teacher_forced(gpu):
 @pytest.mark.parametrize("variant", ["native_exec", "py_blocks", "py_prologue"])
 def test_fused_blocks_match_unfused(gpu, name, variant, monkeypatch):
     """Fused block autograd (weight cache, grad sinks, fused residual-grad, with/without the
-    BN+ReLU conv prologue) == per-op path."""
+    BN+ReLU conv prologue) == per-op path. A norm envelope over the whole flat gradient; the
+    strict, stage-wise check of the native executor is tests/test_gpu_block_oracle.py."""
     from simclr_pytorch_distributed_amd.ops import block, _ext
     monkeypatch.setattr(block, "FUSE_PROLOGUE", variant == "py_prologue")
     monkeypatch.setattr(block, "NATIVE_EXEC", variant == "native_exec")
