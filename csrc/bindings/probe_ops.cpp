@@ -272,6 +272,51 @@ std::vector<torch::Tensor> ce_head_fwd_soft(torch::Tensor x, torch::Tensor W, to
   return {logits, dz, rowstat, stats, loss};
 }
 
+// the teacher's logits and the scalars of the distillation ops (knowledge distillation)
+void check_distill(const char* op, const torch::Tensor& teacher, int64_t B, int64_t C, int dev, double temp,
+                   double alpha) {
+  TORCH_CHECK(teacher.is_cuda() && teacher.scalar_type() == at::kFloat && teacher.is_contiguous() &&
+                  teacher.dim() == 2 && teacher.size(0) == B && teacher.size(1) == C && teacher.get_device() == dev,
+              op, ": teacher_logits: contiguous fp32 [B, C] = [", B, ", ", C, "] on x's device");
+  const float tau = (float)temp;
+  TORCH_CHECK(tau > 0.f && std::isfinite(tau) && std::isfinite(1.f / tau), op,
+              ": temp must be finite and > 0 (in fp32, with its reciprocal), got ", temp);
+  TORCH_CHECK(alpha >= 0.0 && alpha <= 1.0, op, ": alpha must be in [0, 1], got ", alpha);
+}
+
+// ce_head_fwd_soft with a teacher (distill_ce.h): loss = (1 − alpha)·soft CE + alpha·temp²·KL(softmax(
+// teacher_logits / temp) ‖ softmax(logits / temp)), dz its gradient / B; the same five outputs, hits of
+// the logits against `labels`; the backward op is ce_head_bwd, unchanged. alpha = 0 is bit-identical
+// to ce_head_fwd_soft; with alpha = 1 a row whose label lies outside [0, C) is valid and scores no hit.
+std::vector<torch::Tensor> ce_head_fwd_distill(torch::Tensor x, torch::Tensor W, torch::Tensor b,
+                                               torch::Tensor labels, torch::Tensor labels2, double lam, double eps,
+                                               torch::Tensor teacher_logits, double temp, double alpha, bool reduce) {
+  const char* op = "ce_head_fwd_distill";
+  check_classifier(x, W, b, labels);
+  const int64_t B = x.size(0), K = x.size(1), C = W.size(0);
+  check_soft(op, labels2, B, x.get_device(), lam, eps);
+  check_distill(op, teacher_logits, B, C, x.get_device(), temp, alpha);
+  c10::DeviceGuard dg(x.device());
+  auto fo = x.options();
+  auto logits = torch::empty({B, C}, fo);
+  auto dz = torch::empty({B, C}, fo);
+  auto rowstat = torch::empty({B, 3}, fo);
+  auto stats = torch::empty({3}, fo);
+  auto loss = torch::empty({}, fo);
+  check_hip(launch_linear_ce_fwd_distill(x.data_ptr<float>(), W.data_ptr<float>(), b.data_ptr<float>(),
+                                         labels.data_ptr<int64_t>(), labels2.data_ptr<int64_t>(), (float)lam,
+                                         (float)eps, teacher_logits.data_ptr<float>(), (float)temp, (float)alpha,
+                                         (int)B, (int)K, (int)C, (float)(1.0 / B), logits.data_ptr<float>(),
+                                         dz.data_ptr<float>(), rowstat.data_ptr<float>(), cur_stream()),
+            op);
+  if (reduce)
+    check_hip(launch_ce_head_bwd(nullptr, nullptr, nullptr, (int)B, (int)K, (int)C, nullptr, nullptr, nullptr, nullptr,
+                                 rowstat.data_ptr<float>(), stats.data_ptr<float>(), loss.data_ptr<float>(),
+                                 cur_stream()),
+              "ce_head_stats");
+  return {logits, dz, rowstat, stats, loss};
+}
+
 // Training form, backward (one launch): returns dX [B][K] = gout·dz·W (need_dx), accumulates
 // dW += gout·dzᵀ·x and db += gout·Σ_b dz into the given destinations (contiguous fp32, views of
 // a larger buffer allowed) and writes stats / loss from rowstat. gout: scalar fp32 GPU tensor.
@@ -484,6 +529,40 @@ std::vector<torch::Tensor> ce_head_fwd_soft_mfma(torch::Tensor x, torch::Tensor 
   return {logits, dz, rowstat, stats, loss};
 }
 
+// ce_head_fwd_distill on the MFMA logits GEMM: the logits are ce_head_fwd_mfma's bit for bit, alpha = 0
+// is bit-identical to ce_head_fwd_soft_mfma; the backward op is ce_head_bwd_mfma, unchanged
+std::vector<torch::Tensor> ce_head_fwd_distill_mfma(torch::Tensor x, torch::Tensor W, torch::Tensor b,
+                                                    torch::Tensor labels, torch::Tensor labels2, double lam,
+                                                    double eps, torch::Tensor teacher_logits, double temp,
+                                                    double alpha, bool reduce) {
+  const char* op = "ce_head_fwd_distill_mfma";
+  check_head_gemm_classifier(op, x, W);
+  const int64_t B = x.size(0), K = x.size(1), C = W.size(0);
+  check_f32(b, {C}, "b");
+  TORCH_CHECK(b.get_device() == x.get_device(), op, ": one device");
+  check_labels(labels, B, x.get_device());
+  check_soft(op, labels2, B, x.get_device(), lam, eps);
+  check_distill(op, teacher_logits, B, C, x.get_device(), temp, alpha);
+  c10::DeviceGuard dg(x.device());
+  auto fo = x.options();
+  auto logits = torch::empty({B, C}, fo);
+  auto dz = torch::empty({B, C}, fo);
+  auto rowstat = torch::empty({B, 3}, fo);
+  auto stats = torch::empty({3}, fo);
+  auto loss = torch::empty({}, fo);
+  check_hip(launch_head_gemm_logits_distill(x.data_ptr<float>(), W.data_ptr<float>(), b.data_ptr<float>(),
+                                            labels.data_ptr<int64_t>(), labels2.data_ptr<int64_t>(), (float)lam,
+                                            (float)eps, teacher_logits.data_ptr<float>(), (float)temp, (float)alpha,
+                                            (int)B, (int)K, (int)C, (float)(1.0 / B), logits.data_ptr<float>(),
+                                            dz.data_ptr<float>(), rowstat.data_ptr<float>(), cur_stream()),
+            op);
+  if (reduce)
+    check_hip(launch_head_gemm_stats(1, (int)B, (int)K, (int)C, rowstat.data_ptr<float>(), stats.data_ptr<float>(),
+                                     loss.data_ptr<float>(), cur_stream()),
+              op);
+  return {logits, dz, rowstat, stats, loss};
+}
+
 c10::optional<torch::Tensor> ce_head_bwd_mfma(torch::Tensor x, torch::Tensor dz, torch::Tensor W, torch::Tensor gout,
                                               torch::Tensor rowstat, torch::Tensor stats, torch::Tensor loss, OptT dW,
                                               OptT db, bool need_dx) {
@@ -553,6 +632,15 @@ void register_probe(pybind11::module& m) {
   m.def("ce_head_fwd_soft_mfma", &ce_head_fwd_soft_mfma, "ce_head_fwd_soft on the bf16x3 MFMA logits GEMM",
         pybind11::arg("x"), pybind11::arg("W"), pybind11::arg("b"), pybind11::arg("labels"),
         pybind11::arg("labels2"), pybind11::arg("lam"), pybind11::arg("eps"), pybind11::arg("reduce"));
+  m.def("ce_head_fwd_distill", &ce_head_fwd_distill,
+        "ce_head_fwd_soft blended with the temperature-scaled KL to a teacher's logits (knowledge distillation)",
+        pybind11::arg("x"), pybind11::arg("W"), pybind11::arg("b"), pybind11::arg("labels"),
+        pybind11::arg("labels2"), pybind11::arg("lam"), pybind11::arg("eps"), pybind11::arg("teacher_logits"),
+        pybind11::arg("temp"), pybind11::arg("alpha"), pybind11::arg("reduce"));
+  m.def("ce_head_fwd_distill_mfma", &ce_head_fwd_distill_mfma, "ce_head_fwd_distill on the bf16x3 MFMA logits GEMM",
+        pybind11::arg("x"), pybind11::arg("W"), pybind11::arg("b"), pybind11::arg("labels"),
+        pybind11::arg("labels2"), pybind11::arg("lam"), pybind11::arg("eps"), pybind11::arg("teacher_logits"),
+        pybind11::arg("temp"), pybind11::arg("alpha"), pybind11::arg("reduce"));
   m.def("ce_head_bwd_mfma", &ce_head_bwd_mfma, "ce_head_bwd on bf16x3 MFMA GEMMs", pybind11::arg("x"),
         pybind11::arg("dz"), pybind11::arg("W"), pybind11::arg("gout"), pybind11::arg("rowstat"),
         pybind11::arg("stats"), pybind11::arg("loss"), pybind11::arg("dW"), pybind11::arg("db"),

@@ -35,6 +35,16 @@ hipError_t launch_linear_ce_fwd(const float* x, const float* W, const float* bia
 hipError_t launch_linear_ce_fwd_soft(const float* x, const float* W, const float* bias, const int64_t* labels,
                                      const int64_t* labels2, float lam, float eps, int B, int K, int C, float gscale,
                                      float* logits, float* dz, float* rowstat, hipStream_t s);
+// The DISTILL form (distill_ce.h; plain rows only): the soft form's arguments and `teacher` [B][C],
+// the teacher's fp32 logits; loss = (1 − alpha)·soft CE + alpha·tau²·KL(softmax(teacher / tau) ‖
+// softmax(z / tau)), dz its gradient·gscale, hits of z against `labels`. hipErrorInvalidValue before
+// any launch for a null pointer (dz may be null), tau or 1 / tau not finite and > 0, alpha outside
+// [0, 1], lam / eps outside the soft form's range. alpha = 0 is bit-identical to the soft form;
+// alpha = 1 forms no CE term, and a row with a label outside [0, C) is then valid (no hit)
+hipError_t launch_linear_ce_fwd_distill(const float* x, const float* W, const float* bias, const int64_t* labels,
+                                        const int64_t* labels2, float lam, float eps, const float* teacher, float tau,
+                                        float alpha, int B, int K, int C, float gscale, float* logits, float* dz,
+                                        float* rowstat, hipStream_t s);
 // probe form: gradient + SGD update of (W, b) in place, stats[3] = Σ_rows rowstat
 hipError_t launch_linear_ce_sgd(const float* x, const float* dz, int B, int K, int C, float* W, float* bias,
                                 float* bufW, float* bufb, float lr, float mom, float wd, int first,
@@ -64,6 +74,12 @@ hipError_t launch_head_gemm_logits(const float* x, const float* W, const float* 
 hipError_t launch_head_gemm_logits_soft(const float* x, const float* W, const float* bias, const int64_t* labels,
                                         const int64_t* labels2, float lam, float eps, int B, int K, int C,
                                         float gscale, float* logits, float* dz, float* rowstat, hipStream_t s);
+// The DISTILL form for one head, as launch_linear_ce_fwd_distill: the same logits GEMM, then the
+// distill row kernel; the soft form's alignment rule; alpha = 0 is bit-identical to the soft form
+hipError_t launch_head_gemm_logits_distill(const float* x, const float* W, const float* bias, const int64_t* labels,
+                                           const int64_t* labels2, float lam, float eps, const float* teacher,
+                                           float tau, float alpha, int B, int K, int C, float gscale, float* logits,
+                                           float* dz, float* rowstat, hipStream_t s);
 // 1 launch: stats [G][3] = Σ_rows rowstat (fp64, row order); loss (optional, G = 1) = stats[0] / B
 hipError_t launch_head_gemm_stats(int G, int B, int K, int C, const float* rowstat, float* stats, float* loss,
                                   hipStream_t s);

@@ -45,6 +45,7 @@
 #include <limits.h>
 
 #include "common.h"
+#include "distill_ce.h"
 #include "head_gemm_plan.h"
 #include "launchers.h"
 #include "soft_ce.h"
@@ -389,6 +390,23 @@ __global__ __launch_bounds__(256) void ce_rows_soft_kernel(const float* __restri
               dz != nullptr ? dz + (size_t)row * C : nullptr, rowstat + (size_t)row * 3, lane);
 }
 
+// The DISTILL form of ce_rows_soft_kernel (knowledge distillation: --distill_ckpt): the same grid
+// and rows per block; the row's wave also reads the teacher's logits row (distill_ce.h)
+__global__ __launch_bounds__(256) void ce_rows_distill_kernel(const float* __restrict__ logits,
+                                                              const int64_t* __restrict__ labels,
+                                                              const int64_t* __restrict__ labels2, SoftTarget t,
+                                                              const float* __restrict__ teacher, DistillArgs d, int B,
+                                                              int C, float gscale, float* __restrict__ dz,
+                                                              float* __restrict__ rowstat) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * hg::kRowsPerBlock + (threadIdx.x >> 6);
+  if (row >= B) return;
+  const int64_t la = labels[row], lb = labels2[row];
+  const bool ok = la >= 0 && la < C && lb >= 0 && lb < C;
+  distill_ce_row(logits + (size_t)row * C, teacher + (size_t)row * C, C, ok ? (int)la : -1, ok ? (int)lb : -1, ok, t,
+                 d, gscale, nullptr, dz != nullptr ? dz + (size_t)row * C : nullptr, rowstat + (size_t)row * 3, lane);
+}
+
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 Operand operand(const float* p, int lim_i, int lim_r, long si, long sr, int hc = INT_MAX, long hs = 0) {
@@ -466,6 +484,37 @@ hipError_t launch_head_gemm_logits_soft(const float* x, const float* W, const fl
   SDX_LAUNCH_CHECK();
   hipLaunchKernelGGL(ce_rows_soft_kernel, dim3(pl.row_blocks), dim3(256), 0, s, logits, labels, labels2,
                      make_soft_target(lam, eps, C), B, C, gscale, dz, rowstat);
+  SDX_LAUNCH_CHECK();
+  return hipSuccess;
+}
+
+hipError_t launch_head_gemm_logits_distill(const float* x, const float* W, const float* bias, const int64_t* labels,
+                                           const int64_t* labels2, float lam, float eps, const float* teacher,
+                                           float tau, float alpha, int B, int K, int C, float gscale, float* logits,
+                                           float* dz, float* rowstat, hipStream_t s) {
+  hg::Plan pl;
+  if (!hg::make_plan(1, B, K, C, &pl)) return hipErrorInvalidValue;
+  if (x == nullptr || W == nullptr || bias == nullptr || labels == nullptr || labels2 == nullptr ||
+      teacher == nullptr || logits == nullptr || rowstat == nullptr)
+    return hipErrorInvalidValue;
+  if (!aligned16(x) || !aligned16(W) || !aligned16(logits) || (dz != nullptr && !aligned16(dz)))
+    return hipErrorInvalidValue;
+  if (!(lam >= 0.f && lam <= 1.f) || !(eps >= 0.f && eps < 1.f)) return hipErrorInvalidValue;
+  if (!distill_args_ok(tau, alpha)) return hipErrorInvalidValue;
+  GemmParams p = {};
+  p.a = operand(x, B, K, K, 1);
+  p.b = operand(W, C, K, K, 1);
+  set_form(p, pl.nt);
+  p.G = 1; p.B = B; p.C = C; p.K = K;
+  p.out = logits;
+  p.bias = bias;
+  // the plain launcher's logits GEMM, then the distill row kernel
+  hipLaunchKernelGGL((head_gemm_kernel<kVec, kVec, kLogits>), dim3(pl.nt.tiles), dim3(256), 0, s, p,
+                     RowMap{nullptr, 0});
+  SDX_LAUNCH_CHECK();
+  hipLaunchKernelGGL(ce_rows_distill_kernel, dim3(pl.row_blocks), dim3(256), 0, s, logits, labels, labels2,
+                     make_soft_target(lam, eps, C), teacher, make_distill_args(tau, alpha), B, C, gscale, dz,
+                     rowstat);
   SDX_LAUNCH_CHECK();
   return hipSuccess;
 }

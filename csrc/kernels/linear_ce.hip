@@ -31,6 +31,7 @@
 // cost is launch count and latency, not FLOPs).
 #include "common.h"
 #include "launchers.h"
+#include "distill_ce.h"
 #include "soft_ce.h"
 
 using namespace sdx;
@@ -166,6 +167,53 @@ __global__ __launch_bounds__(256) void linear_ce_fwd_soft_kernel(const float* __
   const bool ok = la >= 0 && la < C && lb >= 0 && lb < C;
   soft_ce_row(z[wv], C, la, lb, ok, t, gscale, logits + (size_t)row * C,
               dz != nullptr ? dz + (size_t)row * C : nullptr, rowstat + (size_t)row * 3, lane);
+}
+
+// The DISTILL form of linear_ce_fwd_kernel<KJ, false> (knowledge distillation: --distill_ckpt): the
+// soft kernel's block and logits loop — copied once more, so that the existing kernels stay the
+// code they were — and distill_ce_row (distill_ce.h). The teacher's logits [B][C] are read from
+// global memory by the row's wave: the block's LDS is the soft kernel's.
+template <int KJ>
+__global__ __launch_bounds__(256) void linear_ce_fwd_distill_kernel(
+    const float* __restrict__ x, const float* __restrict__ W, const float* __restrict__ bias,
+    const int64_t* __restrict__ labels, const int64_t* __restrict__ labels2, SoftTarget t,
+    const float* __restrict__ teacher, DistillArgs d, int B, int C, float gscale, float* __restrict__ logits,
+    float* __restrict__ dz, float* __restrict__ rowstat) {
+  constexpr int K = 64 * KJ;
+  __shared__ float z[kRows][kMaxClasses];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int r0 = blockIdx.x * kRows;
+  float xv[kRows][KJ];
+#pragma unroll
+  for (int r = 0; r < kRows; ++r) {
+    const int row = r0 + r;
+#pragma unroll
+    for (int j = 0; j < KJ; ++j) xv[r][j] = row < B ? x[(size_t)row * K + 64 * j + lane] : 0.f;
+  }
+  for (int c = wv; c < C; c += 4) {
+    const float* wr = W + (size_t)c * K;
+    float acc[kRows] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < KJ; ++j) {
+      const float w = wr[64 * j + lane];
+#pragma unroll
+      for (int r = 0; r < kRows; ++r) acc[r] = fmaf(xv[r][j], w, acc[r]);
+    }
+    const float b = bias[c];
+#pragma unroll
+    for (int r = 0; r < kRows; ++r) {
+      const float s = lane_sum(acc[r]);
+      if (lane == 0) z[r][c] = s + b;
+    }
+  }
+  __syncthreads();
+  const int row = r0 + wv;
+  if (row >= B) return;
+  const int64_t la = labels[row], lb = labels2[row];
+  const bool ok = la >= 0 && la < C && lb >= 0 && lb < C;
+  distill_ce_row(z[wv], teacher + (size_t)row * C, C, ok ? (int)la : -1, ok ? (int)lb : -1, ok, t, d, gscale,
+                 logits + (size_t)row * C, dz != nullptr ? dz + (size_t)row * C : nullptr,
+                 rowstat + (size_t)row * 3, lane);
 }
 
 // grid: ceil(C*K/4 / 256) weight blocks + 1 (bias + statistics); W == nullptr: statistics only.
@@ -342,6 +390,34 @@ hipError_t launch_linear_ce_fwd_soft(const float* x, const float* W, const float
   case KJ:                                                                                                      \
     hipLaunchKernelGGL((linear_ce_fwd_soft_kernel<KJ>), grid, blk, 0, s, x, W, bias, labels, labels2, t, B, C, \
                        gscale, logits, dz, rowstat);                                                            \
+    break;
+    SDX_LCE(1) SDX_LCE(2) SDX_LCE(4) SDX_LCE(8) SDX_LCE(16) SDX_LCE(32)
+#undef SDX_LCE
+    default:
+      return hipErrorInvalidValue;   // K / 64 must be a power of two <= 32
+  }
+  SDX_LAUNCH_CHECK();
+  return hipSuccess;
+}
+
+hipError_t launch_linear_ce_fwd_distill(const float* x, const float* W, const float* bias, const int64_t* labels,
+                                        const int64_t* labels2, float lam, float eps, const float* teacher, float tau,
+                                        float alpha, int B, int K, int C, float gscale, float* logits, float* dz,
+                                        float* rowstat, hipStream_t s) {
+  if (!linear_ce_supported(K, C) || B < 1) return hipErrorInvalidValue;
+  if (x == nullptr || W == nullptr || bias == nullptr || labels == nullptr || labels2 == nullptr ||
+      teacher == nullptr || logits == nullptr || rowstat == nullptr)
+    return hipErrorInvalidValue;
+  if (!(lam >= 0.f && lam <= 1.f) || !(eps >= 0.f && eps < 1.f)) return hipErrorInvalidValue;
+  if (!distill_args_ok(tau, alpha)) return hipErrorInvalidValue;
+  const SoftTarget t = make_soft_target(lam, eps, C);
+  const DistillArgs d = make_distill_args(tau, alpha);
+  const dim3 grid((B + kRows - 1) / kRows), blk(256);
+  switch (K / 64) {
+#define SDX_LCE(KJ)                                                                                               \
+  case KJ:                                                                                                       \
+    hipLaunchKernelGGL((linear_ce_fwd_distill_kernel<KJ>), grid, blk, 0, s, x, W, bias, labels, labels2, t,     \
+                       teacher, d, B, C, gscale, logits, dz, rowstat);                                           \
     break;
     SDX_LCE(1) SDX_LCE(2) SDX_LCE(4) SDX_LCE(8) SDX_LCE(16) SDX_LCE(32)
 #undef SDX_LCE

@@ -3,6 +3,8 @@ loaders (reference main_ce.py:19-68 keeps only ``set_loader``).
 
 Baseline:     python main_ce.py --dataset cifar10 --model resnet50 --epochs 500 --cosine
 Fine-tuning:  python main_ce.py --ckpt path/to/last.pth --label_frac 0.1 --learning_rate 0.05 --epochs 100
+Distillation: python main_ce.py --distill_ckpt path/to/finetuned/last.pth --distill_model resnet50 --model resnet18 \
+                  --distill_temp 1.0 --distill_alpha 1.0 --label_frac 0.1
 Multi GPU:    torchrun --nproc-per-node 8 --master-addr 127.0.0.1 main_ce.py --syncBN ...
 
 ``set_loader(opt)`` returns (train, val) in-memory datasets plus the GPU augmentation

@@ -20,7 +20,9 @@ probe also takes ``--dataset path`` with ``--size`` / ``--mean`` / ``--std``),
 ``--sweep_lr`` / ``--sweep_wd`` (linear probe: one classifier per (lr, wd) pair on one encoder pass),
 ``--cache_features`` / ``--cache_views`` (linear probe: encode the frozen encoder's features once),
 ``--label_smoothing`` / ``--mixup`` / ``--cutmix`` / ``--mix_prob`` / ``--mix_switch_prob`` (supervised
-trainer: soft-target regularisers, data/augment.py ``mix_draw``).
+trainer: soft-target regularisers, data/augment.py ``mix_draw``),
+``--distill_ckpt`` / ``--distill_model`` / ``--distill_temp`` / ``--distill_alpha`` (supervised trainer:
+knowledge distillation from a frozen ``main_ce.py`` checkpoint, the SimCLRv2 stage 3).
 Fixes: ``--num_workers`` is honoured (Q6): it sizes the image-decode thread pool of
 ``dataset=path`` and the CPU augmentation threads of ``--gpu_aug 0`` (the default pipeline
 is the GPU kernel, which needs no workers); ``dataset=path`` parses ``--mean/--std``
@@ -357,6 +359,11 @@ class _CeOptions(_HeadOptions):
     cutmix = 0.0
     mix_prob = 1.0
     mix_switch_prob = 0.5
+    # knowledge distillation (likewise absent from ``vars(opt)`` without --distill_ckpt)
+    distill_ckpt = ""
+    distill_model = None
+    distill_temp = 1.0
+    distill_alpha = 1.0
 
 
 def _add_mix_flags(g):
@@ -401,6 +408,41 @@ def _check_mix_flags(parser, opt):
         if opt.mixup > 0 and opt.cutmix > 0 and opt.mix_switch_prob != 0.5:
             suffix += f"_switch_{opt.mix_switch_prob}"
     return suffix
+
+
+def _add_distill_flags(g):
+    S = argparse.SUPPRESS
+    g.add_argument("--distill_ckpt", type=str, default=S, metavar="PATH",
+                   help="knowledge distillation: a main_ce.py checkpoint whose whole model (encoder and fc) is the "
+                        "frozen teacher; the loss becomes (1 - A) x cross-entropy + A x T^2 x KL(teacher || student) "
+                        "at temperature T")
+    g.add_argument("--distill_model", type=str, default=S, metavar="NAME",
+                   help="the teacher's architecture (with --distill_ckpt); default: --model")
+    g.add_argument("--distill_temp", type=float, default=S, metavar="T",
+                   help="distillation temperature (with --distill_ckpt), > 0; default 1")
+    g.add_argument("--distill_alpha", type=float, default=S, metavar="A",
+                   help="weight of the distillation term (with --distill_ckpt), in [0, 1]; default 1: no label is "
+                        "used and every training image is sampled, whatever --label_frac is")
+
+
+def _check_distill_flags(parser, opt):
+    """The distillation flags: the dependent ones need --distill_ckpt, ranges (a parser error
+    otherwise); -> the model_name suffix."""
+    given = vars(opt)
+    if not given.get("distill_ckpt"):
+        if "distill_ckpt" in given:
+            parser.error("--distill_ckpt needs a path")
+        for name in ("distill_model", "distill_temp", "distill_alpha"):
+            if name in given:
+                parser.error(f"--{name} needs --distill_ckpt")
+        return ""
+    if not 0.0 < opt.distill_temp < math.inf:
+        parser.error(f"--distill_temp {opt.distill_temp} must be finite and > 0")
+    if not 0.0 <= opt.distill_alpha <= 1.0:
+        parser.error(f"--distill_alpha {opt.distill_alpha} must be in [0, 1]")
+    if opt.distill_model is None:
+        opt.distill_model = opt.model
+    return f"_distill_{opt.distill_model}_T_{opt.distill_temp}_a_{opt.distill_alpha}"
 
 
 def _add_head_gemm_flag(g):
@@ -544,6 +586,7 @@ def ce_parser() -> argparse.ArgumentParser:
     _add_eval_flags(g)
     _add_head_gemm_flag(g)
     _add_mix_flags(g)
+    _add_distill_flags(g)
     _add_common_new_flags(p)
     return p
 
@@ -552,7 +595,7 @@ def parse_ce(argv: Optional[Sequence[str]] = None, make_dirs: bool = True,
              now: Optional[datetime.datetime] = None):
     parser = ce_parser()
     opt = parser.parse_args(argv, namespace=_CeOptions())
-    mix_suffix = _check_mix_flags(parser, opt)
+    mix_suffix = _check_mix_flags(parser, opt) + _check_distill_flags(parser, opt)
     if opt.cuda_graph or opt.micro_batch:
         raise ValueError("main_ce.py supports neither --cuda_graph nor --micro_batch")
     if not 0.0 < opt.label_frac <= 1.0:

@@ -19,6 +19,13 @@ Validation folds the CURRENT BatchNorm statistics into the convs (ops/linear_pro
 ``FoldedEncoder``, rebuilt every time: the encoder trains here) and evaluates with the fused
 classifier kernel; ImageFolder runs use the GPU Resize + CenterCrop transform.
 
+``--distill_ckpt`` (knowledge distillation, the SimCLRv2 stage 3): a frozen teacher — the whole
+``model`` of a checkpoint of this trainer, ``fc`` included — encodes every step's views in eval
+mode (native: a ``FoldedEncoder`` built once) and its logits enter the loss node as a constant:
+(1 − α)·cross-entropy + α·τ²·KL(teacher ‖ student) (ops/ce_head.py). The teacher is no part of the
+flat buffer, the optimizer, the reducer or the saved checkpoint; with α = 1 no label is used and
+the sampler runs over the whole training store.
+
 Checkpoints have the reference's 4-key layout (engine/checkpoint.py); their ``encoder.*`` keys
 load into ``main_linear.py --ckpt`` and the whole ``model`` into ``SupCEResNet``.
 """
@@ -31,11 +38,13 @@ import time
 
 import numpy as np
 import torch
+import torch.nn.functional as F
 
 from ..data import augment as aug_mod
 from ..data.augment import AugConfig
 from ..data.sampler import DistributedIndexSampler, label_subset
 from ..data.store import probe_stores
+from ..models.executor import ModelRunner
 from ..models.resnet import SupCEResNet
 from ..ops import _ext, linear_probe
 from ..ops import ce_head
@@ -57,6 +66,27 @@ def load_encoder(model: torch.nn.Module, path: str):
     if lost or not enc:
         raise KeyError(f"{path}: encoder tensors missing from the checkpoint: {lost[:5] or 'all'}")
     return len(enc)
+
+
+def load_teacher(path: str, name: str, n_cls: int, stem: str) -> SupCEResNet:
+    """The distillation teacher: the whole ``model`` of a supervised-trainer checkpoint, ``fc``
+    included, loaded strictly into a ``SupCEResNet`` of architecture ``name``; frozen and in eval
+    mode. A classifier of another width than ``n_cls`` is refused."""
+    sd = ckpt_mod.strip_prefix(ckpt_mod.load_checkpoint(path)["model"])
+    if "fc.weight" not in sd:
+        raise KeyError(f"{path}: no classifier (fc.weight) in the checkpoint: --distill_ckpt takes a main_ce.py "
+                       f"checkpoint")
+    n_teacher = int(sd["fc.weight"].shape[0])
+    if n_teacher != int(n_cls):
+        raise ValueError(f"--distill_ckpt {path}: the teacher classifies {n_teacher} classes (fc.out_features), "
+                         f"the run has n_cls = {int(n_cls)}")
+    with torch.random.fork_rng(devices=[]):      # the teacher's throw-away initial weights draw no student number
+        teacher = SupCEResNet(name, n_teacher, stem)
+    ckpt_mod.load_model_state(teacher, sd, strict=True)
+    teacher.eval()
+    for p in teacher.parameters():
+        p.requires_grad_(False)
+    return teacher
 
 
 class SupervisedEngine(TrainEngine):
@@ -81,6 +111,11 @@ class SupervisedEngine(TrainEngine):
         self.subset = label_subset(self._labels_np, opt.label_frac, opt.seed)
         if opt.label_frac < 1.0:
             logging.info(f"--label_frac {opt.label_frac}: {self.subset.size} of {len(self.train)} training images")
+        if getattr(opt, "distill_ckpt", "") and float(getattr(opt, "distill_alpha", 1.0)) == 1.0:
+            # no label enters the loss: every image is distilled
+            self.subset = np.arange(len(self.train), dtype=np.int64)
+            logging.info(f"--distill_alpha 1: sampling all {self.subset.size} training images whatever --label_frac "
+                         f"is; the stored labels serve only the logged train Acc@1")
         self.sampler = DistributedIndexSampler(int(self.subset.size), opt.local_batch, self.world, self.rank,
                                                seed=opt.seed)
         if len(self.sampler) < 1:
@@ -118,6 +153,45 @@ class SupervisedEngine(TrainEngine):
             if self.smoothing > 0:
                 on.append(f"label_smoothing {self.smoothing}")
             logging.info("soft targets: " + ", ".join(on) + " (train Acc@1 counts the dominant label)")
+        self.teacher = None
+        if getattr(opt, "distill_ckpt", ""):
+            self._build_teacher()
+
+    def _build_teacher(self):
+        """The frozen teacher of --distill_ckpt, built once: on the native backend a
+        ``FoldedEncoder`` (it never changes) and, where the classifier kernels take its shape,
+        the name of their evaluation op for its logits."""
+        opt = self.opt
+        name = getattr(opt, "distill_model", None) or opt.model
+        self.distill_temp = float(getattr(opt, "distill_temp", 1.0))
+        self.distill_alpha = float(getattr(opt, "distill_alpha", 1.0))
+        teacher = load_teacher(opt.distill_ckpt, name, opt.n_cls, opt.stem).to(self.device)
+        if self.device.type == "cuda":
+            teacher = teacher.to(memory_format=torch.channels_last)
+        self.teacher = teacher
+        self._teacher_step = None
+        if self.backend == "native":
+            self._teacher_encode = linear_probe.FoldedEncoder(teacher.encoder)
+            for gemm in dict.fromkeys((getattr(opt, "head_gemm", "fma"), "fma")):
+                if linear_probe.supported(teacher, gemm=gemm):
+                    self._teacher_step = "linear_ce_step_mfma" if gemm == "mfma" else "linear_ce_step"
+                    break
+        else:
+            runner = ModelRunner(teacher, "torch", opt.precision)
+            self._teacher_encode = lambda x: runner.encode(x, training=False)
+        logging.info(f"distillation: teacher {name} from {opt.distill_ckpt}, temperature {self.distill_temp}, "
+                     f"alpha {self.distill_alpha}, {self.subset.size} training images sampled")
+
+    @torch.no_grad()
+    def _teacher_logits(self, x: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+        """The teacher's fp32 logits [B, n_cls] of the step's views, queued on the compute stream."""
+        fc = self.teacher.fc
+        feat = self._teacher_encode(x).float()
+        if self._teacher_step is not None:
+            # the classifier kernels' evaluation form (as validate): logits only, nothing is updated
+            return getattr(_ext.require(), self._teacher_step)(feat.contiguous(), fc.weight, fc.bias, labels.long().contiguous(), None, None,
+                                      0.0, 0.0, 0.0, False, False)[0]
+        return F.linear(feat, fc.weight, fc.bias)
 
     def head_gemm(self) -> str:
         """--head_gemm where it can run; else the default path, with one warning line."""
@@ -145,6 +219,10 @@ class SupervisedEngine(TrainEngine):
         if self.mixing or self.smoothing > 0:
             x, soft = self._mix(x, labels, epoch, it)
             labels = soft.pop("labels")
+        if self.teacher is not None:
+            with ph("teacher"):
+                soft.update(teacher_logits=self._teacher_logits(x, labels), temp=self.distill_temp,
+                            alpha=self.distill_alpha)
         with ph("forward"):
             feat = self.runner.encode(x)
         with ph("loss"):
