@@ -21,12 +21,9 @@
 // shortcuts (:50-55) on the pipelined kernel (an x chunk reads its pixel at base + step·const
 // when a step is whole output rows, else from g / Q per step). The layer-1 1x1 wgrads (64
 // channels on one side, HBM-bound) run on the same kernel over a pixel-pair view (w1_pairs).
-#include <atomic>
-#include <type_traits>
-
 #include "common.h"
 #include "launchers.h"
-#include "mfma_lds.h"
+#include "wgrad_tile.h"
 
 using namespace sdx;
 
@@ -56,7 +53,7 @@ struct W1Params {
   const uint16_t* x;    // [P][C]
   float* part;          // [splits][K][C]
   int K, C;
-  int steps_total;      // dy pixels / 32
+  WgSplit g;            // steps_total = dy pixels / 32
   // x pixel of dy pixel j of a step (pipelined kernel): stride 1: j; stride st (H = st·P,
   // W = st·Q, Q | 32): st·(W·(j / Q) + j % Q). x step stride in elements (32·C at stride 1;
   // 0 for the GEN kernels)
@@ -66,34 +63,69 @@ struct W1Params {
   // g = 32·step + j is xst·(xw·(g / Q) + g % Q), with g / Q = umulhi(g, xmagic) (exact for
   // g·Q < 2^32, host check)
   unsigned xmagic;
-  int steps_per_split;
-  int k_tiles, c_tiles, splits;
   // pixel pairs (a 64-channel side, stride 1): K, C above are the doubled widths of the
   // [pixels / 2][2·K0] / [pixels / 2][2·C0] views; only the diagonal blocks (even pixel x even
   // pixel, odd x odd) are stored, into slices 2·split and 2·split + 1 of a [2·splits][K0][C0] slab
   int pairs, K0, C0;
 };
 
+// One 32-pixel step's LDS stage of a BM x BN block tile: the dy image [32][BM], then the x
+// image [32][BN]; the wave tile is BM/2 rows x BN/4 columns = TM x TN MFMA tiles
+template <int BM, int BN>
+struct W1Stage {
+  static constexpr int A_BYTES = 32 * BM * 2, B_BYTES = 32 * BN * 2;
+  static constexpr int STAGE = A_BYTES + B_BYTES;
+  static constexpr int A_CPR = BM / 8, B_CPR = BN / 8;    // 16-B chunks per image row
+  static constexpr int TM = BM / 32, TN = BN / 64;
+};
+
+// Stage byte offsets of a lane's fragments (step-invariant; WgLane): pixel row p_lo, columns
+// col0 + 4pp .. +3. Pixel row p_hi = p_lo + 4 differs from p_lo in row bit 2 only, which the
+// swizzle ignores: its fragment half sits a constant 4 rows further (an immediate ds_read
+// offset, w1_read_frags)
+template <int BM, int BN>
+__device__ __forceinline__ void w1_frag_offsets(const WgLane& L, int (&ao)[BM / 32], int (&bo)[BN / 64]) {
+  using G = W1Stage<BM, BN>;
+  auto kout = [&](auto cols_tag, int col0) __attribute__((always_inline)) {
+    constexpr int COLS = decltype(cols_tag)::value;
+    const int col = col0 + 4 * L.pp;
+    return w1_off<COLS>(L.p_lo, col >> 3) + (col & 7) * 2;
+  };
+#pragma unroll
+  for (int i = 0; i < G::TM; ++i) ao[i] = kout(WgI<BM>{}, L.wm * (16 * G::TM) + 16 * i);
+#pragma unroll
+  for (int j = 0; j < G::TN; ++j) bo[j] = G::A_BYTES + kout(WgI<BN>{}, L.wn * (16 * G::TN) + 16 * j);
+}
+template <int BM, int BN>
+__device__ __forceinline__ void w1_read_frags(const unsigned char* b, const int (&ao)[BM / 32],
+                                              const int (&bo)[BN / 64], bf16x8 (&fa)[BM / 32],
+                                              bf16x8 (&fb)[BN / 64]) {
+#pragma unroll
+  for (int j = 0; j < BN / 64; ++j) fb[j] = wg_frag<4 * BN * 2>(b, bo[j]);
+#pragma unroll
+  for (int i = 0; i < BM / 32; ++i) fa[i] = wg_frag<4 * BM * 2>(b, ao[i]);
+}
+
+// 128-row epilogue (wgrad1x1_kernel, wgrad1x1_pipe_kernel): the pair view's diagonal blocks, or
+// the split's slab
+template <int TN>
+__device__ __forceinline__ void w1_store(const W1Params& p, const f32x4 (&acc)[4][TN], const WgTile& t,
+                                         const WgLane& L) {
+  if (p.pairs) wg_store_pairs(acc, p.part, p.K0, p.C0, t, L);
+  else wg_store_1x1(acc, p.part, p.K, p.C, t, L);
+}
+
 template <int BN>
 __global__ __launch_bounds__(W1_NT, 1) void wgrad1x1_kernel(W1Params p) {
-  constexpr int A_BYTES = 32 * W1_BM * 2;
-  constexpr int STAGE = A_BYTES + 32 * BN * 2;
-  constexpr int A_CPR = W1_BM / 8, B_CPR = BN / 8;        // 16-B chunks per image row
+  using G = W1Stage<W1_BM, BN>;
+  constexpr int A_BYTES = G::A_BYTES, STAGE = G::STAGE, A_CPR = G::A_CPR, B_CPR = G::B_CPR, TN = G::TN;
   constexpr int NCH = 32 * (A_CPR + B_CPR) / W1_NT;       // chunks per thread per step
   static_assert(NCH == 2 || NCH == 3, "loader layout");
-  constexpr int WN_COLS = BN / 4, TN = WN_COLS / 16;      // wave tile: 64 rows x BN/4 columns
   __shared__ __attribute__((aligned(16))) unsigned char smem[2 * STAGE];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int h4 = lane >> 4, c16 = lane & 15;
-  const int wm = wv >> 2, wn = wv & 3;
-
-  // ---- tile / split (split-major: an XCD's co-resident blocks share one pixel range) ----
-  const int tiles = p.k_tiles * p.c_tiles;
-  const int lin = xcd_remap(blockIdx.x, gridDim.x);
-  const int tile = lin % tiles, split = lin / tiles;
-  const int k0 = (tile / p.c_tiles) * W1_BM, c0 = (tile % p.c_tiles) * BN;
-  const int s_begin = split * p.steps_per_split;
-  const int s_end = min(p.steps_total, s_begin + p.steps_per_split);
+  const int tid = threadIdx.x;
+  const WgLane L(tid);
+  const WgTile t = wg_tile<W1_BM, BN>(p.g);
+  const int k0 = t.k0, c0 = t.c0, s_begin = t.s_begin, s_end = t.s_end;
 
   // ---- loader: chunk f = tid + u·512 (u < NCH); f < 512: dy chunk (pixel f/16, channel
   // chunk f%16 of the 128 rows), else x chunk e = f − 512 (pixel e/B_CPR, chunk e%B_CPR) ----
@@ -118,12 +150,6 @@ __global__ __launch_bounds__(W1_NT, 1) void wgrad1x1_kernel(W1Params p) {
     uint4 a, b, c;
   };
   Regs r0, r1, r2, r3;
-  auto slot = [&](auto S) -> Regs& {
-    if constexpr (decltype(S)::value == 0) return r0;
-    else if constexpr (decltype(S)::value == 1) return r1;
-    else if constexpr (decltype(S)::value == 2) return r2;
-    else return r3;
-  };
   auto ld = [&](const Chunk& ck, int step, bool ok) -> uint4 {
     return *reinterpret_cast<const uint4*>(ok ? ck.base + (long)step * ck.stride : g_zero16);
   };
@@ -140,63 +166,28 @@ __global__ __launch_bounds__(W1_NT, 1) void wgrad1x1_kernel(W1Params p) {
     if constexpr (NCH == 3) *reinterpret_cast<uint4*>(sb + ck2.dst) = r.c;
   };
 
-  // ---- fragment offsets (step-invariant): lane (h4, c16 = 4q + pp) reads pixel rows
-  // 8h4+q and +4, columns col0 + 4pp .. +3 ----
-  const int q = c16 >> 2, pp = c16 & 3;
-  const int p_lo = 8 * h4 + q, p_hi = p_lo + 4;
-  auto kout = [&](auto cols_tag, int row, int col0) {
-    constexpr int COLS = decltype(cols_tag)::value;
-    const int col = col0 + 4 * pp;
-    return w1_off<COLS>(row, col >> 3) + (col & 7) * 2;
-  };
-  int ao_lo[4], ao_hi[4], bo_lo[TN], bo_hi[TN];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    ao_lo[i] = kout(std::integral_constant<int, W1_BM>{}, p_lo, wm * 64 + 16 * i);
-    ao_hi[i] = kout(std::integral_constant<int, W1_BM>{}, p_hi, wm * 64 + 16 * i);
-  }
-#pragma unroll
-  for (int j = 0; j < TN; ++j) {
-    bo_lo[j] = A_BYTES + kout(std::integral_constant<int, BN>{}, p_lo, wn * WN_COLS + 16 * j);
-    bo_hi[j] = A_BYTES + kout(std::integral_constant<int, BN>{}, p_hi, wn * WN_COLS + 16 * j);
-  }
-  auto frag = [&](const unsigned char* b, int o_lo, int o_hi) -> bf16x8 {
-    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4*)(b + o_lo));
-    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4*)(b + o_hi));
-    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-  };
-
+  int ao[4], bo[TN];
+  w1_frag_offsets<W1_BM, BN>(L, ao, bo);
   f32x4 acc[4][TN];
+  // (its own zeroing loop: with wg_zero the BN = 256 instantiation allocates 202 VGPRs for 194)
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
     for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
   auto compute = [&](int buf) {
-    const unsigned char* b = smem + buf * STAGE;
     bf16x8 af[4], bfr[TN];
-#pragma unroll
-    for (int j = 0; j < TN; ++j) bfr[j] = frag(b, bo_lo[j], bo_hi[j]);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) af[i] = frag(b, ao_lo[i], ao_hi[i]);
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[j], af[i], acc[i][j], 0, 0, 0);
+    w1_read_frags<W1_BM, BN>(smem + buf * STAGE, ao, bo, af, bfr);
+    wg_mfma(af, bfr, acc);
   };
 
   // ---- K loop (as wgrad3x3.hip): compute step k from LDS buffer k&1, move step k+1 from
   // its ring slot into the other buffer, refill the slot with step k+1+4, one barrier ----
-  using I0 = std::integral_constant<int, 0>;
-  using I1 = std::integral_constant<int, 1>;
-  using I2 = std::integral_constant<int, 2>;
-  using I3 = std::integral_constant<int, 3>;
   auto iter = [&](int b0, auto U) {
     constexpr int u = decltype(U)::value;
-    using N = std::integral_constant<int, (u + 1) % W1_PF>;
+    constexpr int N = (u + 1) % W1_PF;
     compute(u & 1);
-    store((u + 1) & 1, slot(N{}));
-    load(b0 + u + 1 + W1_PF, slot(N{}));
+    store((u + 1) & 1, wg_slot<N>(r0, r1, r2, r3));
+    load(b0 + u + 1 + W1_PF, wg_slot<N>(r0, r1, r2, r3));
     __syncthreads();
   };
   load(s_begin, r0);
@@ -207,45 +198,13 @@ __global__ __launch_bounds__(W1_NT, 1) void wgrad1x1_kernel(W1Params p) {
   load(s_begin + W1_PF, r0);
   __syncthreads();
   for (int b0 = s_begin; b0 < s_end; b0 += W1_PF) {
-    iter(b0, I0{});
-    iter(b0, I1{});
-    iter(b0, I2{});
-    iter(b0, I3{});
+    iter(b0, WgI<0>{});
+    iter(b0, WgI<1>{});
+    iter(b0, WgI<2>{});
+    iter(b0, WgI<3>{});
   }
 
-  // ---- epilogue: fp32 partial rows, 4 consecutive columns per lane ----
-  if (p.pairs) {
-    // the diagonal blocks only: row m of dy half e = m / K0, column n of x half n / C0 (4
-    // consecutive columns never straddle C0, a multiple of 64)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int m = k0 + wm * 64 + 16 * i + c16;
-      const int e = m >= p.K0;
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        const int n = c0 + wn * WN_COLS + 16 * j + 4 * h4;
-        if ((n >= p.C0) != e) continue;
-        const f32x4 a = acc[i][j];
-        float* o = p.part + ((size_t)(2 * split + e) * p.K0 + (m - e * p.K0)) * p.C0 + (n - e * p.C0);
-        st16<SDX_NT_PART != 0>(o, make_uint4(__float_as_uint(a[0]), __float_as_uint(a[1]), __float_as_uint(a[2]),
-                                             __float_as_uint(a[3])));
-      }
-    }
-    return;
-  }
-  float* out = p.part + (size_t)split * p.K * p.C;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int m = k0 + wm * 64 + 16 * i + c16;
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      const int n = c0 + wn * WN_COLS + 16 * j + 4 * h4;
-      const f32x4 a = acc[i][j];
-      st16<SDX_NT_PART != 0>(out + (size_t)m * p.C + n,
-                             make_uint4(__float_as_uint(a[0]), __float_as_uint(a[1]), __float_as_uint(a[2]),
-                                        __float_as_uint(a[3])));
-    }
-  }
+  w1_store(p, acc, t, L);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -262,23 +221,15 @@ __global__ __launch_bounds__(W1_NT, 1) void wgrad1x1_kernel(W1Params p) {
 // per kernel: profiles/ablate_wgrad_r3.txt.)
 template <int BN, bool GEN>
 __global__ __launch_bounds__(W1_NT, 1) void wgrad1x1_pipe_kernel(W1Params p) {
-  constexpr int A_BYTES = 32 * W1_BM * 2;
-  constexpr int STAGE = A_BYTES + 32 * BN * 2;
-  constexpr int A_CPR = W1_BM / 8, B_CPR = BN / 8;
+  using G = W1Stage<W1_BM, BN>;
+  constexpr int A_BYTES = G::A_BYTES, STAGE = G::STAGE, A_CPR = G::A_CPR, B_CPR = G::B_CPR, TN = G::TN;
   constexpr int NCH = 32 * (A_CPR + B_CPR) / W1_NT;
   static_assert(NCH == 2 || NCH == 3, "loader layout");
-  constexpr int WN_COLS = BN / 4, TN = WN_COLS / 16;
   __shared__ __attribute__((aligned(16))) unsigned char smem[3 * STAGE];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int h4 = lane >> 4, c16 = lane & 15;
-  const int wm = wv >> 2, wn = wv & 3;
-
-  const int tiles = p.k_tiles * p.c_tiles;
-  const int lin = xcd_remap(blockIdx.x, gridDim.x);
-  const int tile = lin % tiles, split = lin / tiles;
-  const int k0 = (tile / p.c_tiles) * W1_BM, c0 = (tile % p.c_tiles) * BN;
-  const int s_begin = split * p.steps_per_split;
-  const int s_end = min(p.steps_total, s_begin + p.steps_per_split);
+  const int tid = threadIdx.x;
+  const WgLane L(tid);
+  const WgTile t = wg_tile<W1_BM, BN>(p.g);
+  const int k0 = t.k0, c0 = t.c0, s_begin = t.s_begin, s_end = t.s_end;
 
   // loader: chunk u of this thread (u < NCH) is a dy chunk (pixel f/16 of the 32-pixel
   // step, channel chunk f%16 of the 128 rows) for f = tid + 512u < 512, else an x chunk;
@@ -303,8 +254,7 @@ __global__ __launch_bounds__(W1_NT, 1) void wgrad1x1_pipe_kernel(W1Params p) {
   const int x_dst1 = A_BYTES + w1_off<BN>(e1 / B_CPR, e1 % B_CPR);
   const int x_dst2 = A_BYTES + w1_off<BN>(e2 / B_CPR, e2 % B_CPR);
   const int sA = 32 * p.K, sB = p.x_step;
-  gptr16 zp = (gptr16)g_zero16;
-  asm volatile("" : "+s"(zp));
+  const gptr16 zp = opaque_zero();
   const gptr16 gdy = (gptr16)p.dy, gx = (gptr16)p.x;
   // native vectors (a HIP uint4 read through an address-space-1 pointer becomes a memcpy
   // that keeps the ring in scratch)
@@ -313,12 +263,6 @@ __global__ __launch_bounds__(W1_NT, 1) void wgrad1x1_pipe_kernel(W1Params p) {
     u32x4 a, b, c;
   };
   Regs r0, r1, r2, r3;
-  auto slot = [&](auto S) __attribute__((always_inline)) -> Regs& {
-    if constexpr (decltype(S)::value == 0) return r0;
-    else if constexpr (decltype(S)::value == 1) return r1;
-    else if constexpr (decltype(S)::value == 2) return r2;
-    else return r3;
-  };
   typedef const __attribute__((address_space(1))) u32x4* g16;
   auto load = [&](int step, Regs& r) __attribute__((always_inline)) {
     const bool ok = step < s_end;
@@ -337,61 +281,27 @@ __global__ __launch_bounds__(W1_NT, 1) void wgrad1x1_pipe_kernel(W1Params p) {
     if constexpr (NCH == 3) *reinterpret_cast<u32x4*>(sb + x_dst2) = r.c;
   };
 
-  const int q = c16 >> 2, pp = c16 & 3;
-  const int p_lo = 8 * h4 + q;   // fragment pixel rows p_lo and p_lo + 4
-  auto kout = [&](auto cols_tag, int row, int col0) __attribute__((always_inline)) {
-    constexpr int COLS = decltype(cols_tag)::value;
-    const int col = col0 + 4 * pp;
-    return w1_off<COLS>(row, col >> 3) + (col & 7) * 2;
-  };
-  // pixel row p_hi = p_lo + 4 differs from p_lo in row bit 2 only, which the swizzle
-  // ignores: its fragment half sits a constant 4 rows further (an immediate ds_read offset)
   int ao[4], bo[TN];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) ao[i] = kout(std::integral_constant<int, W1_BM>{}, p_lo, wm * 64 + 16 * i);
-#pragma unroll
-  for (int j = 0; j < TN; ++j) bo[j] = A_BYTES + kout(std::integral_constant<int, BN>{}, p_lo, wn * WN_COLS + 16 * j);
-  auto frag = [&](const unsigned char* b, int o, auto cols_tag) __attribute__((always_inline)) -> bf16x8 {
-    constexpr int COLS = decltype(cols_tag)::value;
-    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4*)(b + o));
-    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4*)(b + o + 4 * COLS * 2));
-    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-  };
-
+  w1_frag_offsets<W1_BM, BN>(L, ao, bo);
   f32x4 acc[4][TN];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  wg_zero(acc);
 
   // fragment register sets (named, selected at compile time by step parity)
   bf16x8 fa0[4], fb0[TN], fa1[4], fb1[TN];
   auto read_frags = [&](const unsigned char* b, bf16x8 (&fa)[4], bf16x8 (&fb)[TN]) {
-#pragma unroll
-    for (int j = 0; j < TN; ++j) fb[j] = frag(b, bo[j], std::integral_constant<int, BN>{});
-#pragma unroll
-    for (int i = 0; i < 4; ++i) fa[i] = frag(b, ao[i], std::integral_constant<int, W1_BM>{});
+    w1_read_frags<W1_BM, BN>(b, ao, bo, fa, fb);
   };
-  auto mfmas = [&](const bf16x8 (&fa)[4], const bf16x8 (&fb)[TN]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[j], fa[i], acc[i][j], 0, 0, 0);
-  };
+  auto mfmas = [&](const bf16x8 (&fa)[4], const bf16x8 (&fb)[TN]) { wg_mfma(fa, fb, acc); };
 
   // LDS buffers of steps k, k+1, k+2 (rotating)
   unsigned char* b_cur = smem;
   unsigned char* b_nxt = smem + STAGE;
   unsigned char* b_st = smem + 2 * STAGE;
-  using I0 = std::integral_constant<int, 0>;
-  using I1 = std::integral_constant<int, 1>;
-  using I2 = std::integral_constant<int, 2>;
-  using I3 = std::integral_constant<int, 3>;
   // iteration for step k = base + U: read step k+1's fragments, MFMAs of step k, store step
   // k+2 (ring slot (U+2)%4) into the buffer step k-1 vacated, refill that slot with k+6
   auto iter = [&](int b0, auto U) __attribute__((always_inline)) {
     constexpr int u = decltype(U)::value;
-    using S = std::integral_constant<int, (u + 2) % 4>;
+    constexpr int S = (u + 2) % 4;   // ring slot of step k+2
 #if SDX_W1_ORDER
     // every LDS access of the step (next fragments, the store of step k+2) and the refill
     // loads are ISSUED before this step's MFMAs, so they complete under them: left to
@@ -399,8 +309,8 @@ __global__ __launch_bounds__(W1_NT, 1) void wgrad1x1_pipe_kernel(W1Params p) {
     // lgkmcnt(0) then exposed their whole latency plus the store transfer every step
     if constexpr ((u & 1) == 0) read_frags(b_nxt, fa1, fb1);
     else read_frags(b_nxt, fa0, fb0);
-    store(b_st, slot(S{}));
-    load(b0 + u + 6, slot(S{}));
+    store(b_st, wg_slot<S>(r0, r1, r2, r3));
+    load(b0 + u + 6, wg_slot<S>(r0, r1, r2, r3));
     __builtin_amdgcn_sched_barrier(0);
     if constexpr ((u & 1) == 0) mfmas(fa0, fb0);
     else mfmas(fa1, fb1);
@@ -413,14 +323,14 @@ __global__ __launch_bounds__(W1_NT, 1) void wgrad1x1_pipe_kernel(W1Params p) {
       read_frags(b_nxt, fa0, fb0);
       mfmas(fa1, fb1);
     }
-    store(b_st, slot(S{}));
-    load(b0 + u + 6, slot(S{}));
+    store(b_st, wg_slot<S>(r0, r1, r2, r3));
+    load(b0 + u + 6, wg_slot<S>(r0, r1, r2, r3));
 #endif
     __syncthreads();
-    unsigned char* t = b_cur;
+    unsigned char* vacated = b_cur;
     b_cur = b_nxt;
     b_nxt = b_st;
-    b_st = t;
+    b_st = vacated;
   };
   load(s_begin, r0);
   load(s_begin + 1, r1);
@@ -433,44 +343,13 @@ __global__ __launch_bounds__(W1_NT, 1) void wgrad1x1_pipe_kernel(W1Params p) {
   __syncthreads();
   read_frags(b_cur, fa0, fb0);
   for (int b0 = s_begin; b0 < s_end; b0 += 4) {
-    iter(b0, I0{});
-    iter(b0, I1{});
-    iter(b0, I2{});
-    iter(b0, I3{});
+    iter(b0, WgI<0>{});
+    iter(b0, WgI<1>{});
+    iter(b0, WgI<2>{});
+    iter(b0, WgI<3>{});
   }
 
-  if (p.pairs) {
-    // the diagonal blocks only: row m of dy half e = m / K0, column n of x half n / C0 (4
-    // consecutive columns never straddle C0, a multiple of 64)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int m = k0 + wm * 64 + 16 * i + c16;
-      const int e = m >= p.K0;
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        const int n = c0 + wn * WN_COLS + 16 * j + 4 * h4;
-        if ((n >= p.C0) != e) continue;
-        const f32x4 a = acc[i][j];
-        float* o = p.part + ((size_t)(2 * split + e) * p.K0 + (m - e * p.K0)) * p.C0 + (n - e * p.C0);
-        st16<SDX_NT_PART != 0>(o, make_uint4(__float_as_uint(a[0]), __float_as_uint(a[1]), __float_as_uint(a[2]),
-                                             __float_as_uint(a[3])));
-      }
-    }
-    return;
-  }
-  float* out = p.part + (size_t)split * p.K * p.C;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int m = k0 + wm * 64 + 16 * i + c16;
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      const int n = c0 + wn * WN_COLS + 16 * j + 4 * h4;
-      const f32x4 a = acc[i][j];
-      st16<SDX_NT_PART != 0>(out + (size_t)m * p.C + n,
-                             make_uint4(__float_as_uint(a[0]), __float_as_uint(a[1]), __float_as_uint(a[2]),
-                                        __float_as_uint(a[3])));
-    }
-  }
+  w1_store(p, acc, t, L);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -521,27 +400,19 @@ __device__ __forceinline__ void w1_glds16(gptr16 src, uint32_t lds_addr) {
 
 template <int BN>
 __global__ __launch_bounds__(W1_NT, 1) void wgrad1x1_big_kernel(W1Params p) {
-  constexpr int A_BYTES = 32 * W1B_BM * 2;             // 16 KiB
-  constexpr int B_BYTES = 32 * BN * 2;                 // 16 / 8 KiB
-  constexpr int STAGE = A_BYTES + B_BYTES;
+  using G = W1Stage<W1B_BM, BN>;                       // wave tile 128 x BN/4
+  constexpr int A_BYTES = G::A_BYTES, B_BYTES = G::B_BYTES, STAGE = G::STAGE;   // 16 + 16 / 8 KiB
   constexpr int ND_A = A_BYTES / 1024 / 8;             // DMAs per wave per step: 2
   constexpr int ND_B = B_BYTES / 1024 / 8;             // 2 / 1
   constexpr int ND = ND_A + ND_B;
-  constexpr int A_CPR = W1B_BM / 8, B_CPR = BN / 8;     // 16-B chunks per image row
+  constexpr int A_CPR = G::A_CPR, B_CPR = G::B_CPR;
   constexpr int A_RPD = 64 / A_CPR, B_RPD = 64 / B_CPR; // image rows per wave-DMA
-  constexpr int WN_COLS = BN / 4, TN = WN_COLS / 16;   // wave tile 128 x BN/4
-  constexpr int TM = 8;
+  constexpr int TM = G::TM, TN = G::TN;
   __shared__ __attribute__((aligned(1024))) unsigned char smem[W1B_NS * STAGE];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int h4 = lane >> 4, c16 = lane & 15;
-  const int wm = wv >> 2, wn = wv & 3;
-
-  const int tiles = p.k_tiles * p.c_tiles;
-  const int lin = xcd_remap(blockIdx.x, gridDim.x);
-  const int tile = lin % tiles, split = lin / tiles;
-  const int k0 = (tile / p.c_tiles) * W1B_BM, c0 = (tile % p.c_tiles) * BN;
-  const int s_begin = split * p.steps_per_split;
-  const int s_end = min(p.steps_total, s_begin + p.steps_per_split);
+  const WgLane L(threadIdx.x);
+  const int lane = L.lane, wv = L.wv;
+  const WgTile t = wg_tile<W1B_BM, BN>(p.g);
+  const int k0 = t.k0, c0 = t.c0, s_begin = t.s_begin, s_end = t.s_end;
 
   // ---- DMA sources (32-bit element offsets of step 0; host check P*K, H*W*C < 2^31) ----
   int a_src[ND_A], b_src[ND_B];
@@ -559,8 +430,7 @@ __global__ __launch_bounds__(W1_NT, 1) void wgrad1x1_big_kernel(W1Params p) {
     b_src[i] = xp * p.C + c0 + ((s ^ kout_swz<BN>(r)) << 3);
   }
   const int sA = 32 * p.K, sB = p.x_step;
-  gptr16 zp = (gptr16)g_zero16;
-  asm volatile("" : "+s"(zp));
+  const gptr16 zp = opaque_zero();
   const gptr16 gdy = (gptr16)p.dy, gx = (gptr16)p.x;
   const uint32_t lds0 = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) unsigned char*)smem;
   auto issue = [&](int step) __attribute__((always_inline)) {
@@ -574,33 +444,11 @@ __global__ __launch_bounds__(W1_NT, 1) void wgrad1x1_big_kernel(W1Params p) {
       w1_glds16(ok ? gx + (b_src[i] + step * sB) : zp, st + A_BYTES + (wv * ND_B + i) * 1024);
   };
 
-  // ---- fragment offsets (as wgrad1x1_pipe_kernel) ----
-  const int q = c16 >> 2, pp = c16 & 3;
-  const int p_lo = 8 * h4 + q;
-  auto kout = [&](auto cols_tag, int row, int col0) __attribute__((always_inline)) {
-    constexpr int COLS = decltype(cols_tag)::value;
-    const int col = col0 + 4 * pp;
-    return w1_off<COLS>(row, col >> 3) + (col & 7) * 2;
-  };
-  // stage-0 byte offsets of the fragments (a stage adds k % 4 · STAGE); pixel row p_hi =
-  // p_lo + 4 is a constant 4·COLS·2 bytes further (the swizzle ignores row bit 2)
+  // stage-0 byte offsets of the fragments (a stage adds k % 4 · STAGE)
   int ao[TM], bo[TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i) ao[i] = kout(std::integral_constant<int, W1B_BM>{}, p_lo, wm * 128 + 16 * i);
-#pragma unroll
-  for (int j = 0; j < TN; ++j) bo[j] = A_BYTES + kout(std::integral_constant<int, BN>{}, p_lo, wn * WN_COLS + 16 * j);
-  auto frag = [&](const unsigned char* b, int o, auto cols_tag) __attribute__((always_inline)) -> bf16x8 {
-    constexpr int HI = 4 * decltype(cols_tag)::value * 2;
-    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4*)(b + o));
-    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4*)(b + o + HI));
-    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-  };
-
+  w1_frag_offsets<W1B_BM, BN>(L, ao, bo);
   f32x4 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  wg_zero(acc);
 
   // Software-pipelined over two named fragment sets: iteration k waits for step k+1's DMA,
   // passes the barrier (its lgkmcnt(0) also completes step k's fragment reads, issued one
@@ -608,11 +456,7 @@ __global__ __launch_bounds__(W1_NT, 1) void wgrad1x1_big_kernel(W1Params p) {
   // slot (every wave has finished reading it: the barrier), then runs step k's MFMAs on the
   // fragments in registers -- the reads and the DMA fly under the MFMAs.
   auto read_set = [&](int k, bf16x8 (&fa)[TM], bf16x8 (&fb)[TN]) __attribute__((always_inline)) {
-    const unsigned char* b = smem + (k % W1B_NS) * STAGE;
-#pragma unroll
-    for (int j = 0; j < TN; ++j) fb[j] = frag(b, bo[j], std::integral_constant<int, BN>{});
-#pragma unroll
-    for (int i = 0; i < TM; ++i) fa[i] = frag(b, ao[i], std::integral_constant<int, W1B_BM>{});
+    w1_read_frags<W1B_BM, BN>(smem + (k % W1B_NS) * STAGE, ao, bo, fa, fb);
   };
   auto iter = [&](int k, bf16x8 (&ca)[TM], bf16x8 (&cb)[TN], bf16x8 (&na)[TM], bf16x8 (&nb)[TN])
       __attribute__((always_inline)) {
@@ -620,10 +464,7 @@ __global__ __launch_bounds__(W1_NT, 1) void wgrad1x1_big_kernel(W1Params p) {
     lds_barrier();
     read_set(k + 1, na, nb);
     issue(k + 4);
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cb[j], ca[i], acc[i][j], 0, 0, 0);
+    wg_mfma(ca, cb, acc);
   };
   bf16x8 fa0[TM], fb0[TN], fa1[TM], fb1[TN];
   issue(s_begin);
@@ -639,19 +480,7 @@ __global__ __launch_bounds__(W1_NT, 1) void wgrad1x1_big_kernel(W1Params p) {
   }
   vm_wait<0>();   // the tail DMAs (zero page) land before the block's LDS is released
 
-  float* out = p.part + (size_t)split * p.K * p.C;
-#pragma unroll
-  for (int i = 0; i < TM; ++i) {
-    const int m = k0 + wm * 128 + 16 * i + c16;
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      const int n = c0 + wn * WN_COLS + 16 * j + 4 * h4;
-      const f32x4 a = acc[i][j];
-      st16<SDX_NT_PART != 0>(out + (size_t)m * p.C + n,
-                             make_uint4(__float_as_uint(a[0]), __float_as_uint(a[1]), __float_as_uint(a[2]),
-                                        __float_as_uint(a[3])));
-    }
-  }
+  wg_store_1x1(acc, p.part, p.K, p.C, t, L);
 }
 
 }  // namespace
@@ -669,7 +498,7 @@ hipError_t launch_wgrad1x1(const ConvGeom& g, const sdx_plan::WgradPlan& plan, c
   p.C0 = g.C;
   p.K = w.Kv;
   p.C = w.Cv;
-  p.steps_total = w.steps;
+  p.g.steps_total = w.steps;
   if (g.stride == 1) {
     p.xst = 1, p.xq = 32, p.xw = 32;   // xpix(j) = j
     p.x_step = 32 * p.C;
@@ -678,15 +507,15 @@ hipError_t launch_wgrad1x1(const ConvGeom& g, const sdx_plan::WgradPlan& plan, c
     p.x_step = 32 % g.Q == 0 ? g.stride * g.W * (32 / g.Q) * g.C : 0;
     p.xmagic = (unsigned)((1ULL << 32) / (unsigned)g.Q + 1);
   }
-  p.steps_per_split = plan.per;
-  p.splits = plan.splits;
+  p.g.steps_per_split = plan.per;
+  p.g.splits = plan.splits;
   const int bn = w.bn;
-  p.k_tiles = w.k_tiles;
-  p.c_tiles = w.c_tiles;
+  p.g.k_tiles = w.k_tiles;
+  p.g.c_tiles = w.c_tiles;
   const bool direct = plan.direct && !accumulate;
   if (!direct && partial == nullptr) return hipErrorInvalidValue;
   p.part = direct ? dw : partial;
-  const dim3 grid(p.k_tiles * p.c_tiles * p.splits), block(W1_NT);
+  const dim3 grid(p.g.k_tiles * p.g.c_tiles * p.g.splits), block(W1_NT);
   switch (w.kind) {
     case sdx_plan::W1_BIG:
       if (bn == 256) hipLaunchKernelGGL(wgrad1x1_big_kernel<256>, grid, block, 0, s, p);

@@ -25,11 +25,9 @@
 // as D = Bᵀ·Aᵀ, so each lane holds 4 consecutive output columns of one output row. Output:
 // an fp32 partial slab per K-split, reduced deterministically by the split-K reduction of
 // splitk.hip (no atomics).
-#include <type_traits>
-
 #include "common.h"
 #include "launchers.h"
-#include "mfma_lds.h"
+#include "wgrad_tile.h"
 
 using namespace sdx;
 
@@ -62,11 +60,87 @@ struct W3Params {
   const uint16_t* x;    // [N*H*W][C]
   float* part;          // [splits][K][9*C]
   int K, C;
-  int steps_total;      // N*H*W / 32
-  int steps_per_split;
-  int k_tiles, c_tiles, splits;
+  WgSplit g;            // steps_total = N*H*W / 32
   int h, w;             // image size (wgrad3x3_pad_kernel)
 };
+
+// ---- fragment addressing: the byte offsets of a lane's 2 A + 9 B fragments (lo/hi pixel
+// rows, WgLane) within a stage are step-invariant: computed once. xrow(px, r, s) is the
+// x-window row that tap (r, s) reads for pixel px of the step ----
+struct W3Frags {
+  int ao_lo[2], ao_hi[2], bo_lo[9], bo_hi[9];
+};
+// byte offset within an image of the lane's 4 columns col0 + 4pp .. +3 of LDS row `row`
+__device__ __forceinline__ int w3_lane_off(const WgLane& L, int row, int col0) {
+  const int col = col0 + 4 * L.pp;
+  return w3_off(row, col >> 3) + (col & 7) * 2;
+}
+template <class XRow>
+__device__ __forceinline__ W3Frags w3_frags(const WgLane& L, XRow xrow) {
+  const int p_lo = L.p_lo, p_hi = p_lo + 4;
+  W3Frags f;
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    f.ao_lo[i] = w3_lane_off(L, p_lo, L.wm * 32 + 16 * i);
+    f.ao_hi[i] = w3_lane_off(L, p_hi, L.wm * 32 + 16 * i);
+  }
+#pragma unroll
+  for (int j = 0; j < 9; ++j) {
+    const int n = L.wn * 144 + 16 * j;             // wave column tile: one tap, 16 channels
+    const int t = n >> 6, r = t / 3, s = t - 3 * r;
+    f.bo_lo[j] = W3_DY_BYTES + w3_lane_off(L, xrow(p_lo, r, s), n & 63);
+    f.bo_hi[j] = W3_DY_BYTES + w3_lane_off(L, xrow(p_hi, r, s), n & 63);
+  }
+  return f;
+}
+
+// one step's fragment reads and MFMAs from the stage at `base`
+__device__ __forceinline__ void w3_compute(const unsigned char* base, const W3Frags& f, f32x4 (&acc)[2][9]) {
+  bf16x8 af[2], bfr[9];
+#pragma unroll
+  for (int j = 0; j < 9; ++j) bfr[j] = wg_frag(base, f.bo_lo[j], f.bo_hi[j]);
+#pragma unroll
+  for (int i = 0; i < 2; ++i) af[i] = wg_frag(base, f.ao_lo[i], f.ao_hi[i]);
+  wg_mfma(af, bfr, acc);
+}
+
+// K loop over a 2-step register ring r0, r1 (wgrad3x3_s2_kernel, wgrad3x3_pad_kernel: more
+// chunks per thread than wgrad3x3_kernel, so half its ring depth keeps the VGPRs at its
+// level): compute step k from LDS buffer k&1, move step k+1 from its slot into the other
+// buffer, refill the slot with step k+3. load(step, regs), store(buf, regs) and compute(buf)
+// are the kernel's
+template <class Regs, class Load, class Store, class Compute>
+__device__ __forceinline__ void w3_ring2(const WgTile& t, Regs& r0, Regs& r1, Load load, Store store,
+                                         Compute compute) {
+  auto iter = [&](int base, auto U) {
+    constexpr int u = decltype(U)::value;
+#if !SDX_W3_ORDER
+    compute(u);
+#endif
+    if constexpr (u == 0) {   // slot 1 holds step base+1
+      store(1, r1);
+      load(base + 3, r1);
+    } else {                  // slot 0 holds step base+2
+      store(0, r0);
+      load(base + 4, r0);
+    }
+#if SDX_W3_ORDER
+    __builtin_amdgcn_sched_barrier(0);
+    compute(u);
+    __builtin_amdgcn_sched_barrier(0);
+#endif
+    __syncthreads();
+  };
+  load(t.s_begin, r0);
+  load(t.s_begin + 1, r1);
+  store(0, r0);
+  load(t.s_begin + 2, r0);
+  __syncthreads();
+  for (int base = t.s_begin; base < t.s_end; base += 2) {
+    iter(base, WgI<0>{});
+    iter(base, WgI<1>{});
+  }
+}
 
 template <int W>
 struct W3Geom {
@@ -75,6 +149,8 @@ struct W3Geom {
   static_assert(P >= W + 2, "pad columns");
   static constexpr int XROWS = 3 * RPS * P;                            // LDS rows of the x window
   static constexpr int STAGE = W3_DY_BYTES + XROWS * W3_ROWB;
+  // x-window row of pixel px of the step, tap (r, s) (wgrad3x3_pad_kernel: slot px of SW = W)
+  static __device__ __forceinline__ int xrow(int px, int r, int s) { return (px / W) * P + px % W + r * RPS * P + s; }
 };
 
 template <int W>
@@ -82,17 +158,10 @@ __global__ __launch_bounds__(W3_NT, 1) void wgrad3x3_kernel(W3Params p) {
   using G = W3Geom<W>;
   constexpr int RPS = G::RPS;
   __shared__ __attribute__((aligned(16))) unsigned char smem[2 * G::STAGE];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int h4 = lane >> 4, c16 = lane & 15;
-  const int wm = wv >> 2, wn = wv & 3;
-
-  // ---- tile / split (split-major: an XCD's co-resident blocks share one pixel range) ----
-  const int tiles = p.k_tiles * p.c_tiles;
-  const int lin = xcd_remap(blockIdx.x, gridDim.x);
-  const int tile = lin % tiles, split = lin / tiles;
-  const int k0 = (tile / p.c_tiles) * 64, c0 = (tile % p.c_tiles) * 64;
-  const int s_begin = split * p.steps_per_split;
-  const int s_end = min(p.steps_total, s_begin + p.steps_per_split);
+  const int tid = threadIdx.x;
+  const WgLane L(tid);
+  const WgTile t = wg_tile<64, 64>(p.g);
+  const int k0 = t.k0, c0 = t.c0, s_end = t.s_end;
 
   // ---- zero the pad columns of both x windows (never written by the loads) ----
   for (int e = tid; e < 2 * 3 * RPS * 2 * 8; e += W3_NT) {
@@ -103,17 +172,15 @@ __global__ __launch_bounds__(W3_NT, 1) void wgrad3x3_kernel(W3Params p) {
 
   // ---- loader: 1024 16-B chunks per step, 2 per thread: chunk tid is a dy chunk for the
   // first 256 threads and an x-window chunk otherwise; chunk tid + 512 is always x ----
-  // x-window chunk e (0..767): channel chunk e%8 of pixel w of window row ri = (r, i)
   // Per-thread loader state, fixed for the whole K loop: a step moves every chunk by 32
   // pixels (dy: 32 rows of K; x: RPS image rows of W pixels = 32 pixels of C), so a load is
   // base + step·stride plus, for x, the validity of its source row. Steps at or past s_end
   // (the unrolled loop's tail) load the zero page: they add nothing.
   // x-window chunk e (0..767): channel chunk e%8 of pixel w of window row ri = (r, i)
-  // zero page pinned in an SGPR pair: otherwise every select re-materialises its address
-  // (s_getpc + a GOT load + lgkmcnt(0), which also drains this wave's LDS traffic) and the
-  // divergent selects become exec-masked branches
-  gptr16 zp = (gptr16)g_zero16;
-  asm volatile("" : "+s"(zp));
+  // zero page pinned in an SGPR pair (opaque_zero): otherwise every select re-materialises
+  // its address (s_getpc + a GOT load + lgkmcnt(0), which also drains this wave's LDS
+  // traffic) and the divergent selects become exec-masked branches
+  const gptr16 zp = opaque_zero();
   struct XChunk {
     gptr16 base;   // x element of step 0 (may lie outside x: used only when valid)
     int i, r;       // window image row within the step, tap row
@@ -139,21 +206,8 @@ __global__ __launch_bounds__(W3_NT, 1) void wgrad3x3_kernel(W3Params p) {
   const int dst1 = x_dst(e1);
   const XChunk xc0 = x_chunk(first_dy ? 0 : e0), xc1 = x_chunk(e1);
   const gptr16 dy_base = (gptr16)p.dy + (long)(tid >> 3) * p.K + k0 + (tid & 7) * 8;
-  // register ring of 4 prefetched steps: slot u holds the step ≡ s_begin + u (mod 4). Named
-  // registers selected at compile time (an array indexed inside the lambdas goes to scratch)
+  // register ring of 4 prefetched steps: slot u holds the step ≡ s_begin + u (mod 4)
   w3_u32x4 ra0, rb0, ra1, rb1, ra2, rb2, ra3, rb3;
-  auto slot_a = [&](auto U) -> w3_u32x4& {
-    if constexpr (decltype(U)::value == 0) return ra0;
-    else if constexpr (decltype(U)::value == 1) return ra1;
-    else if constexpr (decltype(U)::value == 2) return ra2;
-    else return ra3;
-  };
-  auto slot_b = [&](auto U) -> w3_u32x4& {
-    if constexpr (decltype(U)::value == 0) return rb0;
-    else if constexpr (decltype(U)::value == 1) return rb1;
-    else if constexpr (decltype(U)::value == 2) return rb2;
-    else return rb3;
-  };
   auto load = [&](int step, w3_u32x4& a, w3_u32x4& b) {
     const gptr16 s0 = first_dy ? (step < s_end ? dy_base + (long)step * 32 * p.K : zp) : x_src(xc0, step);
     a = *(w3_g16)s0;
@@ -164,116 +218,53 @@ __global__ __launch_bounds__(W3_NT, 1) void wgrad3x3_kernel(W3Params p) {
     *reinterpret_cast<w3_u32x4*>(smem + buf * G::STAGE + dst1) = b;
   };
 
-  // ---- fragment addressing: lane (h4, c16 = 4q + pp) reads K rows (pixels) 8h4+q and +4,
-  // columns col0 + 4pp .. +3 (ds_read_b64_tr_b16 transposes across the 4 q-lanes). The byte
-  // offsets are step-invariant: computed once (2 A + 9 B fragments, lo/hi rows). ----
-  const int q = c16 >> 2, pp = c16 & 3;
-  const int p_lo = 8 * h4 + q, p_hi = p_lo + 4;
-  const int xb_lo = (p_lo / W) * G::P + (p_lo % W);   // x-window row of pixel p, tap (0, 0)
-  const int xb_hi = (p_hi / W) * G::P + (p_hi % W);
-  auto lane_off = [&](int row, int col0) {
-    const int col = col0 + 4 * pp;
-    return w3_off(row, col >> 3) + (col & 7) * 2;
-  };
-  int ao_lo[2], ao_hi[2], bo_lo[9], bo_hi[9];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    ao_lo[i] = lane_off(p_lo, wm * 32 + 16 * i);
-    ao_hi[i] = lane_off(p_hi, wm * 32 + 16 * i);
-  }
-#pragma unroll
-  for (int j = 0; j < 9; ++j) {
-    const int n = wn * 144 + 16 * j;             // wave column tile: one tap, 16 channels
-    const int t = n >> 6, r = t / 3, s = t - 3 * r;
-    const int off = r * RPS * G::P + s;
-    bo_lo[j] = W3_DY_BYTES + lane_off(xb_lo + off, n & 63);
-    bo_hi[j] = W3_DY_BYTES + lane_off(xb_hi + off, n & 63);
-  }
-  auto frag = [&](const unsigned char* base, int o_lo, int o_hi) -> bf16x8 {
-    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4*)(base + o_lo));
-    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4*)(base + o_hi));
-    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-  };
-
+  const W3Frags fo = w3_frags(L, G::xrow);
   f32x4 acc[2][9];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 9; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  auto compute = [&](int buf) {
-    const unsigned char* base = smem + buf * G::STAGE;
-    bf16x8 af[2], bfr[9];
-#pragma unroll
-    for (int j = 0; j < 9; ++j) bfr[j] = frag(base, bo_lo[j], bo_hi[j]);
-#pragma unroll
-    for (int i = 0; i < 2; ++i) af[i] = frag(base, ao_lo[i], ao_hi[i]);
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 9; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[j], af[i], acc[i][j], 0, 0, 0);
-  };
+  wg_zero(acc);
+  auto compute = [&](int buf) { w3_compute(smem + buf * G::STAGE, fo, acc); };
 
   // ---- K loop: two LDS buffers, one barrier per step. The loads of step k+1+W3_PF are
   // issued as step k+1 leaves the ring for LDS, so W3_PF steps of loads are always in
   // flight: one step's MFMAs (~300 cycles a wave) are far shorter than an HBM miss. The loop
   // is unrolled by W3_PF (even) and runs whole groups, so ring slots and LDS parity are
   // compile-time. ----
-  using I0 = std::integral_constant<int, 0>;
-  using I1 = std::integral_constant<int, 1>;
-  using I2 = std::integral_constant<int, 2>;
-  using I3 = std::integral_constant<int, 3>;
   // step k = base + U of the unrolled loop: compute from LDS buffer U&1, move step k+1 from
   // its ring slot into the other buffer, refill that slot with step k+1+4. Branch-free (the
   // tail steps read zeros), so the compiler's vmcnt waits retire only the oldest step's loads
   auto iter = [&](int base, auto U) {
-    constexpr int u = decltype(U)::value;
-    using N = std::integral_constant<int, (u + 1) % W3_PF>;
+    constexpr int u = decltype(U)::value, n = (u + 1) % W3_PF;
+    w3_u32x4& na = wg_slot<n>(ra0, ra1, ra2, ra3);
+    w3_u32x4& nb = wg_slot<n>(rb0, rb1, rb2, rb3);
 #if SDX_W3_ORDER
     // the store of step k+1 (other buffer) and the refill loads issue before step k's
     // fragment reads + MFMAs and complete under them instead of in front of the barrier
-    store((u + 1) & 1, slot_a(N{}), slot_b(N{}));
-    load(base + u + 1 + W3_PF, slot_a(N{}), slot_b(N{}));
+    store((u + 1) & 1, na, nb);
+    load(base + u + 1 + W3_PF, na, nb);
     __builtin_amdgcn_sched_barrier(0);
     compute(u & 1);
     __builtin_amdgcn_sched_barrier(0);
 #else
     compute(u & 1);
-    store((u + 1) & 1, slot_a(N{}), slot_b(N{}));
-    load(base + u + 1 + W3_PF, slot_a(N{}), slot_b(N{}));
+    store((u + 1) & 1, na, nb);
+    load(base + u + 1 + W3_PF, na, nb);
 #endif
     __syncthreads();
   };
-  load(s_begin, ra0, rb0);
-  load(s_begin + 1, ra1, rb1);
-  load(s_begin + 2, ra2, rb2);
-  load(s_begin + 3, ra3, rb3);
+  load(t.s_begin, ra0, rb0);
+  load(t.s_begin + 1, ra1, rb1);
+  load(t.s_begin + 2, ra2, rb2);
+  load(t.s_begin + 3, ra3, rb3);
   store(0, ra0, rb0);
-  load(s_begin + W3_PF, ra0, rb0);
+  load(t.s_begin + W3_PF, ra0, rb0);
   __syncthreads();
-  for (int base = s_begin; base < s_end; base += W3_PF) {
-    iter(base, I0{});
-    iter(base, I1{});
-    iter(base, I2{});
-    iter(base, I3{});
+  for (int base = t.s_begin; base < s_end; base += W3_PF) {
+    iter(base, WgI<0>{});
+    iter(base, WgI<1>{});
+    iter(base, WgI<2>{});
+    iter(base, WgI<3>{});
   }
 
-  // ---- epilogue: fp32 partial rows, 4 consecutive columns (same tap) per lane ----
-  const int Ncol = 9 * p.C;
-  float* out = p.part + (size_t)split * p.K * Ncol;
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int m = k0 + wm * 32 + 16 * i + c16;
-#pragma unroll
-    for (int j = 0; j < 9; ++j) {
-      const int n = wn * 144 + 16 * j + 4 * h4;
-      const int t = n >> 6;
-      const f32x4 a = acc[i][j];
-      st16<SDX_NT_PART != 0>(out + (size_t)m * Ncol + t * p.C + c0 + (n & 63),
-                             make_uint4(__float_as_uint(a[0]), __float_as_uint(a[1]), __float_as_uint(a[2]),
-                                        __float_as_uint(a[3])));
-    }
-  }
+  wg_store_3x3(acc, p.part, p.K, p.C, t, L);
 }
 
 
@@ -292,7 +283,7 @@ __global__ __launch_bounds__(W3_NT, 1) void wgrad3x3_kernel(W3Params p) {
 // swizzle stays conflict-free; the window row pitch PT keeps pixels 8 apart at a distance
 // ≡ 8 (mod 16) rows (Q = 8: PT = 24; Q = 4: two output rows, PT = 12). Per step: 256 dy
 // chunks + 3·RPS·2Q·8 = 1536 x chunks (every input column of 3·RPS input rows), 3.5 per
-// thread; a 2-deep register ring keeps VGPRs at the stride-1 kernel's level.
+// thread; a 2-deep register ring (w3_ring2) keeps VGPRs at the stride-1 kernel's level.
 template <int Q>
 struct W3S2Geom {
   static constexpr int RPS = 32 / Q;
@@ -302,6 +293,12 @@ struct W3S2Geom {
   static constexpr int STAGE = W3_DY_BYTES + XROWS * W3_ROWB;
   static constexpr int XCH = 3 * RPS * 2 * Q * 8;    // x chunks per step (1536)
   static_assert(XCH == 1536, "loader layout");
+  // pixel px = (i, wo) = (px / Q, px % Q); tap (r, s) reads window row r·RPS + i at O[wo]
+  // (s = 0), E[wo] (s = 1), O[wo + 1] (s = 2)
+  static __device__ __forceinline__ int xrow(int px, int r, int s) {
+    const int i = px / Q, wo = px % Q;
+    return (r * RPS + i) * PT + (s == 1 ? Q + 1 + wo : wo + (s >> 1));
+  }
 };
 
 // PAD: output width pq = p.w / 2 < Q slots (not a power of two: the 224x224 config's 28 / 14 /
@@ -312,16 +309,10 @@ __global__ __launch_bounds__(W3_NT, 1) void wgrad3x3_s2_kernel(W3Params p) {
   constexpr int RPS = G::RPS, W = 2 * Q;
   const int Wr = PAD ? p.w : W, pq = PAD ? p.w / 2 : Q;   // real input / output widths
   __shared__ __attribute__((aligned(16))) unsigned char smem[2 * G::STAGE];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int h4 = lane >> 4, c16 = lane & 15;
-  const int wm = wv >> 2, wn = wv & 3;
-
-  const int tiles = p.k_tiles * p.c_tiles;
-  const int lin = xcd_remap(blockIdx.x, gridDim.x);
-  const int tile = lin % tiles, split = lin / tiles;
-  const int k0 = (tile / p.c_tiles) * 64, c0 = (tile % p.c_tiles) * 64;
-  const int s_begin = split * p.steps_per_split;
-  const int s_end = min(p.steps_total, s_begin + p.steps_per_split);
+  const int tid = threadIdx.x;
+  const WgLane L(tid);
+  const WgTile t = wg_tile<64, 64>(p.g);
+  const int k0 = t.k0, c0 = t.c0, s_end = t.s_end;
 
   // zero pads O[0] of every window row in both buffers (never written by the loads)
   for (int e = tid; e < 2 * 3 * RPS * 8; e += W3_NT) {
@@ -334,8 +325,7 @@ __global__ __launch_bounds__(W3_NT, 1) void wgrad3x3_s2_kernel(W3Params p) {
   // chunk f%8), else x chunk e = f − 256: channel chunk e%8 of input column e/8 % 2Q of
   // window row ri = e/(16Q) = (r, i). Output row Rg = step·RPS + i (global over images, H =
   // 2P) reads input row 2Rg + r − 1: x element base + step·(2·RPS·W·C)
-  gptr16 zp = (gptr16)g_zero16;   // pinned in SGPRs (see wgrad3x3_kernel)
-  asm volatile("" : "+s"(zp));
+  const gptr16 zp = opaque_zero();   // pinned in SGPRs (see wgrad3x3_kernel)
   struct XChunk {
     gptr16 base;   // element of step 0 (used only when valid)
     int i, r, dst;
@@ -366,120 +356,47 @@ __global__ __launch_bounds__(W3_NT, 1) void wgrad3x3_s2_kernel(W3Params p) {
   const long dy_step = PAD ? (long)RPS * pq * p.K : 32L * p.K;
   const gptr16 dy_base =
       (gptr16)p.dy + (long)(PAD ? (dslot / Q) * pq + dslot % Q : dslot) * p.K + k0 + (tid & 7) * 8;
-  // 2-step register ring of named vectors (a struct of uint4 read through the lambdas ends up
-  // in scratch)
-  w3_u32x4 ra0, rb0, rc0, rd0, ra1, rb1, rc1, rd1;
-  auto load = [&](int step, w3_u32x4& a, w3_u32x4& b, w3_u32x4& c, w3_u32x4& d) {
-    a = *(w3_g16)(first_dy ? (step < s_end && dy_ok ? dy_base + (long)step * dy_step : zp) : x_src(xa, step));
-    b = *(w3_g16)x_src(xb, step);
-    c = *(w3_g16)x_src(xc_, step);
-    d = *(w3_g16)(last_x ? x_src(xd, step) : zp);
+  // ring slots of native vectors (a struct of HIP uint4 read through the lambdas ends up in
+  // scratch)
+  struct Regs {
+    w3_u32x4 a, b, c, d;
   };
-  auto store = [&](int buf, const w3_u32x4& a, const w3_u32x4& b, const w3_u32x4& c, const w3_u32x4& d) {
+  Regs r0, r1;
+  auto load = [&](int step, Regs& r) {
+    r.a = *(w3_g16)(first_dy ? (step < s_end && dy_ok ? dy_base + (long)step * dy_step : zp) : x_src(xa, step));
+    r.b = *(w3_g16)x_src(xb, step);
+    r.c = *(w3_g16)x_src(xc_, step);
+    r.d = *(w3_g16)(last_x ? x_src(xd, step) : zp);
+  };
+  auto store = [&](int buf, const Regs& r) {
     unsigned char* sb = smem + buf * G::STAGE;
-    *reinterpret_cast<w3_u32x4*>(sb + dst_a) = a;
-    *reinterpret_cast<w3_u32x4*>(sb + xb.dst) = b;
-    *reinterpret_cast<w3_u32x4*>(sb + xc_.dst) = c;
-    if (last_x) *reinterpret_cast<w3_u32x4*>(sb + xd.dst) = d;
+    *reinterpret_cast<w3_u32x4*>(sb + dst_a) = r.a;
+    *reinterpret_cast<w3_u32x4*>(sb + xb.dst) = r.b;
+    *reinterpret_cast<w3_u32x4*>(sb + xc_.dst) = r.c;
+    if (last_x) *reinterpret_cast<w3_u32x4*>(sb + xd.dst) = r.d;
   };
 
-  // fragments (as wgrad3x3_kernel): pixel p = (i, wo) = (p / Q, p % Q); tap (r, s) reads
-  // window row r·RPS + i at O[wo] (s = 0), E[wo] (s = 1), O[wo + 1] (s = 2)
-  const int q = c16 >> 2, pp = c16 & 3;
-  const int p_lo = 8 * h4 + q, p_hi = p_lo + 4;
-  auto lane_off = [&](int row, int col0) {
-    const int col = col0 + 4 * pp;
-    return w3_off(row, col >> 3) + (col & 7) * 2;
-  };
-  auto xrow = [&](int px, int r, int s_) {
-    const int i = px / Q, wo = px % Q;
-    return (r * RPS + i) * G::PT + (s_ == 1 ? Q + 1 + wo : wo + (s_ >> 1));
-  };
-  int ao_lo[2], ao_hi[2], bo_lo[9], bo_hi[9];
+  // this kernel's own copy of w3_frags over G::xrow: through the shared builder three of its
+  // instantiations allocate 2 more VGPRs, Q = 8 thereby one more 8-register granule (210 for 208)
+  const int p_lo = L.p_lo, p_hi = p_lo + 4;
+  W3Frags fo;
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
-    ao_lo[i] = lane_off(p_lo, wm * 32 + 16 * i);
-    ao_hi[i] = lane_off(p_hi, wm * 32 + 16 * i);
+    fo.ao_lo[i] = w3_lane_off(L, p_lo, L.wm * 32 + 16 * i);
+    fo.ao_hi[i] = w3_lane_off(L, p_hi, L.wm * 32 + 16 * i);
   }
 #pragma unroll
   for (int j = 0; j < 9; ++j) {
-    const int n = wn * 144 + 16 * j;
-    const int t = n >> 6, r = t / 3, s_ = t - 3 * r;
-    bo_lo[j] = W3_DY_BYTES + lane_off(xrow(p_lo, r, s_), n & 63);
-    bo_hi[j] = W3_DY_BYTES + lane_off(xrow(p_hi, r, s_), n & 63);
+    const int n = L.wn * 144 + 16 * j;
+    const int tap = n >> 6, r = tap / 3, s_ = tap - 3 * r;
+    fo.bo_lo[j] = W3_DY_BYTES + w3_lane_off(L, G::xrow(p_lo, r, s_), n & 63);
+    fo.bo_hi[j] = W3_DY_BYTES + w3_lane_off(L, G::xrow(p_hi, r, s_), n & 63);
   }
-  auto frag = [&](const unsigned char* base, int o_lo, int o_hi) -> bf16x8 {
-    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4*)(base + o_lo));
-    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4*)(base + o_hi));
-    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-  };
-
   f32x4 acc[2][9];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 9; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  auto compute = [&](int buf) {
-    const unsigned char* base = smem + buf * G::STAGE;
-    bf16x8 af[2], bfr[9];
-#pragma unroll
-    for (int j = 0; j < 9; ++j) bfr[j] = frag(base, bo_lo[j], bo_hi[j]);
-#pragma unroll
-    for (int i = 0; i < 2; ++i) af[i] = frag(base, ao_lo[i], ao_hi[i]);
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 9; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[j], af[i], acc[i][j], 0, 0, 0);
-  };
+  wg_zero(acc);
+  w3_ring2(t, r0, r1, load, store, [&](int buf) { w3_compute(smem + buf * G::STAGE, fo, acc); });
 
-  // K loop (wgrad3x3_kernel's, with a 2-step register ring): compute step k from buffer k&1,
-  // move step k+1 from its slot into the other buffer, refill the slot with step k+3
-  using I0 = std::integral_constant<int, 0>;
-  using I1 = std::integral_constant<int, 1>;
-  auto iter = [&](int base, auto U) {
-    constexpr int u = decltype(U)::value;
-#if !SDX_W3_ORDER
-    compute(u);
-#endif
-    if constexpr (u == 0) {   // slot 1 holds step base+1
-      store(1, ra1, rb1, rc1, rd1);
-      load(base + 3, ra1, rb1, rc1, rd1);
-    } else {                  // slot 0 holds step base+2
-      store(0, ra0, rb0, rc0, rd0);
-      load(base + 4, ra0, rb0, rc0, rd0);
-    }
-#if SDX_W3_ORDER
-    __builtin_amdgcn_sched_barrier(0);
-    compute(u);
-    __builtin_amdgcn_sched_barrier(0);
-#endif
-    __syncthreads();
-  };
-  load(s_begin, ra0, rb0, rc0, rd0);
-  load(s_begin + 1, ra1, rb1, rc1, rd1);
-  store(0, ra0, rb0, rc0, rd0);
-  load(s_begin + 2, ra0, rb0, rc0, rd0);
-  __syncthreads();
-  for (int base = s_begin; base < s_end; base += 2) {
-    iter(base, I0{});
-    iter(base, I1{});
-  }
-
-  const int Ncol = 9 * p.C;
-  float* out = p.part + (size_t)split * p.K * Ncol;
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int m = k0 + wm * 32 + 16 * i + c16;
-#pragma unroll
-    for (int j = 0; j < 9; ++j) {
-      const int n = wn * 144 + 16 * j + 4 * h4;
-      const int t = n >> 6;
-      const f32x4 a = acc[i][j];
-      st16<SDX_NT_PART != 0>(out + (size_t)m * Ncol + t * p.C + c0 + (n & 63),
-                             make_uint4(__float_as_uint(a[0]), __float_as_uint(a[1]), __float_as_uint(a[2]),
-                                        __float_as_uint(a[3])));
-    }
-  }
+  wg_store_3x3(acc, p.part, p.K, p.C, t, L);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -492,13 +409,14 @@ __global__ __launch_bounds__(W3_NT, 1) void wgrad3x3_s2_kernel(W3Params p) {
 // of segment i holds, for each tap row r, the SW + 2 columns half·SW − 1 … half·SW + SW of
 // image row Rg + r − 1, every one loaded with its own validity (image edge, w >= W), so a
 // half-row segment sees its real neighbours across the split. Fragment images, swizzle and
-// the schedule are wgrad3x3_s2_kernel's (2-step register ring, stores before the MFMAs).
+// the schedule are wgrad3x3_s2_kernel's (w3_ring2: 2-step register ring, stores before the
+// MFMAs).
 template <int WS>
 struct W3PadGeom {
   static constexpr int SW = WS < 32 ? WS : 32;
   static constexpr int SPR = WS / SW;                 // segments per image row
   static constexpr int RPS = 32 / SW;                 // segments per step
-  static constexpr int P = SW == 32 ? 34 : SW == 16 ? 18 : 24;   // as W3Geom<SW>
+  static constexpr int P = W3Geom<SW>::P;
   static constexpr int XROWS = 3 * RPS * P;
   static constexpr int STAGE = W3_DY_BYTES + XROWS * W3_ROWB;
   static constexpr int XCH = 3 * RPS * (SW + 2) * 8;  // x chunks per step (816 / 864 / 960)
@@ -510,20 +428,13 @@ __global__ __launch_bounds__(W3_NT, 1) void wgrad3x3_pad_kernel(W3Params p) {
   using G = W3PadGeom<WS>;
   constexpr int SW = G::SW, SPR = G::SPR, RPS = G::RPS;
   __shared__ __attribute__((aligned(16))) unsigned char smem[2 * G::STAGE];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int h4 = lane >> 4, c16 = lane & 15;
-  const int wm = wv >> 2, wn = wv & 3;
+  const int tid = threadIdx.x;
+  const WgLane L(tid);
   const int W = p.w, H = p.h;
+  const WgTile t = wg_tile<64, 64>(p.g);
+  const int k0 = t.k0, c0 = t.c0, s_end = t.s_end;
 
-  const int tiles = p.k_tiles * p.c_tiles;
-  const int lin = xcd_remap(blockIdx.x, gridDim.x);
-  const int tile = lin % tiles, split = lin / tiles;
-  const int k0 = (tile / p.c_tiles) * 64, c0 = (tile % p.c_tiles) * 64;
-  const int s_begin = split * p.steps_per_split;
-  const int s_end = min(p.steps_total, s_begin + p.steps_per_split);
-
-  gptr16 zp = (gptr16)g_zero16;   // pinned in SGPRs (see wgrad3x3_kernel)
-  asm volatile("" : "+s"(zp));
+  const gptr16 zp = opaque_zero();   // pinned in SGPRs (see wgrad3x3_kernel)
   const gptr16 gdy = (gptr16)p.dy, gx = (gptr16)p.x;
   // loader: chunk f = tid + 512u (u < 3): f < 256 a dy chunk (slot f/8, channel chunk f%8),
   // else x chunk e = f − 256 < XCH: channel chunk e%8 of window column e/8 % (SW+2) of window
@@ -548,105 +459,30 @@ __global__ __launch_bounds__(W3_NT, 1) void wgrad3x3_pad_kernel(W3Params p) {
     const long pix = (long)(rg + c.r - 1) * W + w;
     return ok ? (c.x ? gx + pix * p.C + c0 + c.ch * 8 : gdy + pix * p.K + k0 + c.ch * 8) : zp;
   };
-  w3_u32x4 ra0, rb0, rc0, ra1, rb1, rc1;
-  auto load = [&](int step, w3_u32x4& a, w3_u32x4& b, w3_u32x4& c) {
-    a = *(w3_g16)src(sa, step);
-    b = *(w3_g16)src(sb, step);
-    c = *(w3_g16)src(sc, step);
+  struct Regs {
+    w3_u32x4 a, b, c;
   };
-  auto store = [&](int buf, const w3_u32x4& a, const w3_u32x4& b, const w3_u32x4& c) {
+  Regs r0, r1;
+  auto load = [&](int step, Regs& r) {
+    r.a = *(w3_g16)src(sa, step);
+    r.b = *(w3_g16)src(sb, step);
+    r.c = *(w3_g16)src(sc, step);
+  };
+  auto store = [&](int buf, const Regs& r) {
     unsigned char* s_ = smem + buf * G::STAGE;
-    *reinterpret_cast<w3_u32x4*>(s_ + sa.dst) = a;
-    *reinterpret_cast<w3_u32x4*>(s_ + sb.dst) = b;
-    if (sc.has) *reinterpret_cast<w3_u32x4*>(s_ + sc.dst) = c;
+    *reinterpret_cast<w3_u32x4*>(s_ + sa.dst) = r.a;
+    *reinterpret_cast<w3_u32x4*>(s_ + sb.dst) = r.b;
+    if (sc.has) *reinterpret_cast<w3_u32x4*>(s_ + sc.dst) = r.c;
   };
 
   // fragments: slot p = (i, c) = (p / SW, p % SW); tap (r, s) reads window row r·RPS + i,
-  // column c + s (window column 0 is the segment's column −1)
-  const int q = c16 >> 2, pp = c16 & 3;
-  const int p_lo = 8 * h4 + q, p_hi = p_lo + 4;
-  const int xb_lo = (p_lo / SW) * G::P + (p_lo % SW), xb_hi = (p_hi / SW) * G::P + (p_hi % SW);
-  auto lane_off = [&](int row, int col0) {
-    const int col = col0 + 4 * pp;
-    return w3_off(row, col >> 3) + (col & 7) * 2;
-  };
-  int ao_lo[2], ao_hi[2], bo_lo[9], bo_hi[9];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    ao_lo[i] = lane_off(p_lo, wm * 32 + 16 * i);
-    ao_hi[i] = lane_off(p_hi, wm * 32 + 16 * i);
-  }
-#pragma unroll
-  for (int j = 0; j < 9; ++j) {
-    const int n = wn * 144 + 16 * j;
-    const int t = n >> 6, r = t / 3, s_ = t - 3 * r;
-    const int off = r * RPS * G::P + s_;
-    bo_lo[j] = W3_DY_BYTES + lane_off(xb_lo + off, n & 63);
-    bo_hi[j] = W3_DY_BYTES + lane_off(xb_hi + off, n & 63);
-  }
-  auto frag = [&](const unsigned char* base, int o_lo, int o_hi) -> bf16x8 {
-    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4*)(base + o_lo));
-    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4*)(base + o_hi));
-    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-  };
+  // column c + s (window column 0 is the segment's column −1): W3Geom<SW>'s map
+  const W3Frags fo = w3_frags(L, W3Geom<SW>::xrow);
   f32x4 acc[2][9];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 9; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  auto compute = [&](int buf) {
-    const unsigned char* base = smem + buf * G::STAGE;
-    bf16x8 af[2], bfr[9];
-#pragma unroll
-    for (int j = 0; j < 9; ++j) bfr[j] = frag(base, bo_lo[j], bo_hi[j]);
-#pragma unroll
-    for (int i = 0; i < 2; ++i) af[i] = frag(base, ao_lo[i], ao_hi[i]);
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 9; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[j], af[i], acc[i][j], 0, 0, 0);
-  };
-  using I0 = std::integral_constant<int, 0>;
-  using I1 = std::integral_constant<int, 1>;
-  auto iter = [&](int base, auto U) {
-    constexpr int u = decltype(U)::value;
-    if constexpr (u == 0) {   // slot 1 holds step base+1
-      store(1, ra1, rb1, rc1);
-      load(base + 3, ra1, rb1, rc1);
-    } else {                  // slot 0 holds step base+2
-      store(0, ra0, rb0, rc0);
-      load(base + 4, ra0, rb0, rc0);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    compute(u);
-    __builtin_amdgcn_sched_barrier(0);
-    __syncthreads();
-  };
-  load(s_begin, ra0, rb0, rc0);
-  load(s_begin + 1, ra1, rb1, rc1);
-  store(0, ra0, rb0, rc0);
-  load(s_begin + 2, ra0, rb0, rc0);
-  __syncthreads();
-  for (int base = s_begin; base < s_end; base += 2) {
-    iter(base, I0{});
-    iter(base, I1{});
-  }
+  wg_zero(acc);
+  w3_ring2(t, r0, r1, load, store, [&](int buf) { w3_compute(smem + buf * G::STAGE, fo, acc); });
 
-  const int Ncol = 9 * p.C;
-  float* out = p.part + (size_t)split * p.K * Ncol;
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int m = k0 + wm * 32 + 16 * i + c16;
-#pragma unroll
-    for (int j = 0; j < 9; ++j) {
-      const int n = wn * 144 + 16 * j + 4 * h4;
-      const int t = n >> 6;
-      const f32x4 a = acc[i][j];
-      st16<SDX_NT_PART != 0>(out + (size_t)m * Ncol + t * p.C + c0 + (n & 63),
-                             make_uint4(__float_as_uint(a[0]), __float_as_uint(a[1]), __float_as_uint(a[2]),
-                                        __float_as_uint(a[3])));
-    }
-  }
+  wg_store_3x3(acc, p.part, p.K, p.C, t, L);
 }
 
 }  // namespace
@@ -660,16 +496,16 @@ hipError_t launch_wgrad3x3(const ConvGeom& g, const sdx_plan::WgradPlan& plan, c
   p.x = (const uint16_t*)x;
   p.K = g.K;
   p.C = g.C;
-  p.steps_total = plan.w3.steps;
-  p.steps_per_split = plan.per;
-  p.splits = plan.splits;
-  p.k_tiles = g.K / 64;
-  p.c_tiles = g.C / 64;
+  p.g.steps_total = plan.w3.steps;
+  p.g.steps_per_split = plan.per;
+  p.g.splits = plan.splits;
+  p.g.k_tiles = g.K / 64;
+  p.g.c_tiles = g.C / 64;
   // one split straight into dW (unless accumulating into it)
   const bool direct = plan.direct && !accumulate;
   if (!direct && partial == nullptr) return hipErrorInvalidValue;
   p.part = direct ? dw : partial;
-  const dim3 grid(p.k_tiles * p.c_tiles * p.splits), block(W3_NT);
+  const dim3 grid(p.g.k_tiles * p.g.c_tiles * p.g.splits), block(W3_NT);
   p.h = g.H;
   p.w = g.W;
   const int slot = plan.w3.slot;
@@ -707,5 +543,5 @@ hipError_t launch_wgrad3x3(const ConvGeom& g, const sdx_plan::WgradPlan& plan, c
   }
   SDX_LAUNCH_CHECK();
   if (direct) return hipSuccess;
-  return launch_splitk_reduce(partial, p.splits, (long)g.K * 9 * g.C / 4, dw, accumulate, s);
+  return launch_splitk_reduce(partial, p.g.splits, (long)g.K * 9 * g.C / 4, dw, accumulate, s);
 }

@@ -615,6 +615,14 @@ def wgrad_variants(impl_or_none, shape, cfg, steps, unit=1):
     return runs
 
 
+def wgrad_row(impl, shape, cfg, steps, unit=1, layouts=("krsc",)):
+    """Every run of one weight-gradient row, in both regimes."""
+    for regime in REGIMES:
+        for splits, sink in wgrad_variants(impl, shape, cfg, steps, unit):
+            for layout in layouts if sink else (None,):
+                check_wgrad(impl, shape, regime, cfg, splits, layout)
+
+
 class knob:
     """``with knob(m, "wgrad1x1_big_set", 2):`` — a setter of the extension, restored on exit."""
 

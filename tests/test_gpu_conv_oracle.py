@@ -87,11 +87,7 @@ def test_dgrad_bnstat(impl, shape, regime):
                 K.check_dgrad_bnstat(impl, shape, regime, cfg, sets, "bits", "full", store_masked=1)
 
 
-def _wgrad_row(impl, shape, cfg, steps, unit=1, layouts=("krsc",)):
-    for regime in K.REGIMES:
-        for splits, sink in K.wgrad_variants(impl, shape, cfg, steps, unit):
-            for layout in layouts if sink else (None,):
-                K.check_wgrad(impl, shape, regime, cfg, splits, layout)
+_wgrad_row = K.wgrad_row
 
 
 @pytest.mark.parametrize("shape,cfg", K.WGRAD_GENERIC)
@@ -114,6 +110,16 @@ def test_wgrad_1x1(impl, shape, variant, bn, setter):
         p = K.plan(impl.m, "wgrad", shape, 10)
         assert (p["variant"], p["bn"]) == (variant, bn)
         _wgrad_row(impl, shape, 10, p["steps"])
+
+
+def test_wgrad_1x1_plain(gpu):
+    """wgrad1x1_kernel (W1_PLAIN) is planned only under SDX_W1_PIPE=0, read once per process: the
+    rows of test_wgrad_1x1 at bn 128 and bn 256 in one fresh child, which asserts the variant
+    through conv_plan. One run, no retry."""
+    e = dict(os.environ, SDX_AUTOBUILD="0", SDX_W1_PIPE="0")
+    r = subprocess.run([sys.executable, os.path.join(TESTS, "conv_w1_plain_worker.py")], env=e,
+                       capture_output=True, text=True, timeout=180)
+    assert r.returncode == 0 and "W1-PLAIN-OK" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-3000:])
 
 
 @pytest.mark.parametrize("Kc,C", [(64, 64), (24, 8)])
