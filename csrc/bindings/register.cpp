@@ -15,6 +15,7 @@ void register_comm(pybind11::module& m);
 void register_head(pybind11::module& m);
 void register_probe(pybind11::module& m);
 void register_knn(pybind11::module& m);
+void register_barlow(pybind11::module& m);
 
 void register_ops(pybind11::module& m) {
   register_supcon(m);
@@ -30,5 +31,6 @@ void register_ops(pybind11::module& m) {
   register_head(m);
   register_probe(m);
   register_knn(m);
+  register_barlow(m);
 }
 }  // namespace sdx_bind

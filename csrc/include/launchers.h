@@ -94,6 +94,28 @@ hipError_t launch_head_gemm_bwd(const float* x, const float* dz, const float* W,
                                 const float* gout, float* dX, float* dW, float* db, const float* rowstat,
                                 float* stats, float* loss, hipStream_t s);
 
+// ---- Barlow Twins loss (barlow.hip, barlow_plan.h): bf16x3 MFMA cross-correlation ------
+// z1, z2 [n][D] fp32 (n rows on this rank), sums fp64 [2][2][D] = per view (Σz, Σz²), stats
+// [2][2][D] = per view (μ, rstd), C / G [D][D], r [2][D] = (r1, r2). n_total: the batch size N of
+// the formulas (= n on one rank). Supported: D = 64·j, 64 <= D <= 8192, n >= 1, n·D < 2^31,
+// 16-byte aligned tensors; everything else is hipErrorInvalidValue before any launch.
+bool barlow_supported(long n, long D);
+// 1 launch: the column sums of both views; stats != nullptr also finalises them with n_total, eps
+hipError_t launch_bt_colstats(const float* z1, const float* z2, int n, int D, double* sums, float* stats,
+                              double n_total, float eps, hipStream_t s);
+// 1 launch: stats from (all-reduced) sums
+hipError_t launch_bt_stats_finalize(const double* sums, int D, double n_total, float eps, float* stats,
+                                    hipStream_t s);
+// 1 launch: C = ẑ1ᵀ·ẑ2 / n_total over this rank's rows
+hipError_t launch_bt_xcorr(const float* z1, const float* z2, const float* stats, int n, int D, double n_total,
+                           float* C, hipStream_t s);
+// 2 launches: C -> G in place, r, loss (device scalar); r2_part [D/8][D], loss_part [D/8]
+hipError_t launch_bt_loss_grad(float* C, int D, float lam, double n_total, float* r, float* loss, float* r2_part,
+                               double* loss_part, hipStream_t s);
+// 1 launch: dz1, dz2 [n][D]; g: the upstream scalar gradient in device memory
+hipError_t launch_bt_bwd(const float* z1, const float* z2, const float* G, const float* stats, const float* r,
+                         const float* g, int n, int D, double n_total, float* dz1, float* dz2, hipStream_t s);
+
 // ---- linear-probe sweep: G classifiers on one feature batch (linear_ce_sweep.hip) ----
 // W [G][C][K], bias [G][C], buffers alike, logits / dz [G][B][C], rowstat [G][B][3], stats [G][3].
 // Supported: 1 <= G <= 16, K = 64·2^j <= 2048, 1 <= C <= 1024, B >= 1, G·B·C, B·K and G·C·K

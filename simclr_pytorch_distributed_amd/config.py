@@ -15,6 +15,7 @@ Additions (new flags only; no reference flag changes meaning):
 ``--feat_dim`` (Q11), ``--resume``, ``--cuda_graph``, ``--work_dir``,
 ``--knn_freq`` / ``--knn`` with ``--knn_k`` / ``--knn_t`` (weighted k-NN monitor, engine/knn.py),
 ``--blur_p`` / ``--blur_kernel`` / ``--blur_sigma`` (Gaussian-blur augmentation, data/augment.py),
+``--method BarlowTwins`` with ``--bt_lambda`` (negative-free pretraining objective, losses/barlow.py),
 ``--val_folder`` / ``--resize`` (ImageFolder evaluation: Resize + CenterCrop on the GPU; the linear
 probe also takes ``--dataset path`` with ``--size`` / ``--mean`` / ``--std``),
 ``--sweep_lr`` / ``--sweep_wd`` (linear probe: one classifier per (lr, wd) pair on one encoder pass),
@@ -158,7 +159,7 @@ def pretrain_parser() -> argparse.ArgumentParser:
     p.add_argument("--data_folder", type=str, default=None, help="path to custom dataset")
     p.add_argument("--size", type=int, default=32, help="parameter for RandomResizedCrop")
     # method / temperature (main_supcon.py:59-63)
-    p.add_argument("--method", type=str, default="SimCLR", choices=["SupCon", "SimCLR"])
+    p.add_argument("--method", type=str, default="SimCLR", choices=["SupCon", "SimCLR", "BarlowTwins"])
     p.add_argument("--temp", type=float, default=0.5, help="temperature for loss function")
     # other (main_supcon.py:66-88)
     p.add_argument("--cosine", action="store_true", help="using cosine annealing")
@@ -199,8 +200,14 @@ def pretrain_parser() -> argparse.ArgumentParser:
     g.add_argument("--blur_sigma", type=float, nargs=2, default=[0.1, 2.0], metavar=("LO", "HI"),
                    help="blur sigma is drawn uniformly from [LO, HI]")
     _add_eval_flags(g)
+    g.add_argument("--bt_lambda", type=float, default=argparse.SUPPRESS, metavar="L",
+                   help="--method BarlowTwins: weight of the off-diagonal term of the cross-correlation loss; "
+                        "default 0.0051")
     _add_common_new_flags(p)
     return p
+
+
+BT_LAMBDA = 0.0051
 
 
 def _finish_common(opt, prefix_dirs: bool):
@@ -248,6 +255,11 @@ def parse_pretrain(argv: Optional[Sequence[str]] = None, make_dirs: bool = True,
     opt.blur_sigma = tuple(opt.blur_sigma)
     if not 0.0 <= opt.blur_p <= 1.0 or opt.blur_kernel < 0 or not 0.0 < opt.blur_sigma[0] <= opt.blur_sigma[1]:
         raise ValueError("--blur_p in [0, 1], --blur_kernel >= 0 and --blur_sigma 0 < LO <= HI are required")
+    if opt.method == "BarlowTwins":
+        if not 0.0 <= getattr(opt, "bt_lambda", BT_LAMBDA) < math.inf:
+            raise ValueError("--bt_lambda must be finite and >= 0")
+    elif hasattr(opt, "bt_lambda"):
+        raise ValueError("--bt_lambda needs --method BarlowTwins")
     rank, local_rank, world = env_rank_info(opt.local_rank)
     opt.rank, opt.local_rank = rank, local_rank
     if opt.ngpu is None:

@@ -1,4 +1,4 @@
-"""Contrastive pretraining engine (SimCLR / SupCon) — replaces main_supcon.py:155-406.
+"""Pretraining engine (SimCLR / SupCon / Barlow Twins) — replaces main_supcon.py:155-406.
 
 Per step (reference hot loop: main_supcon.py:253-349):
 
@@ -97,8 +97,15 @@ class PretrainEngine(TrainEngine):
 
     def _init_state(self):
         opt, dev = self.opt, self.device
-        self.criterion = DistributedContrastiveLoss(opt.method, opt.temp, opt.base_temperature, opt.contrast_mode,
-                                                    backend="native" if self.backend == "native" else "torch")
+        loss_backend = "native" if self.backend == "native" else "torch"
+        if opt.method == "BarlowTwins":
+            from ..config import BT_LAMBDA
+            from ..losses.barlow import BarlowTwinsLoss
+            self.criterion = BarlowTwinsLoss(getattr(opt, "bt_lambda", BT_LAMBDA), backend=loss_backend)
+            logging.info("Barlow Twins: --temp, --base_temperature and --contrast_mode are ignored")
+        else:
+            self.criterion = DistributedContrastiveLoss(opt.method, opt.temp, opt.base_temperature,
+                                                        opt.contrast_mode, backend=loss_backend)
         # device-resident step state (so the step body is graph-capturable)
         self.record_norm_mean = torch.zeros((), device=dev)
         self._rnm_valid = torch.zeros((), device=dev)

@@ -1,0 +1,1 @@
+from .barlow import BarlowTwinsLoss, barlow_reference  # noqa: F401

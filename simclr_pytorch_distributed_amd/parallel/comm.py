@@ -333,3 +333,21 @@ def all_reduce_sum_(x: torch.Tensor) -> torch.Tensor:
     if world_size() > 1:
         dist.all_reduce(x)
     return x
+
+
+class _AllReduceGrad(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        return all_reduce_sum_(x.clone())
+
+    @staticmethod
+    def backward(ctx, g):
+        return all_reduce_sum_(g.clone())
+
+
+def all_reduce_with_grad(x: torch.Tensor) -> torch.Tensor:
+    """Sum over ranks; backward: the sum over ranks of the incoming gradients (every rank's
+    output depends on every rank's input)."""
+    if world_size() == 1:
+        return x
+    return _AllReduceGrad.apply(x)
