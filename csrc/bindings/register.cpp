@@ -16,6 +16,7 @@ void register_head(pybind11::module& m);
 void register_probe(pybind11::module& m);
 void register_knn(pybind11::module& m);
 void register_barlow(pybind11::module& m);
+void register_vicreg(pybind11::module& m);
 
 void register_ops(pybind11::module& m) {
   register_supcon(m);
@@ -32,5 +33,6 @@ void register_ops(pybind11::module& m) {
   register_probe(m);
   register_knn(m);
   register_barlow(m);
+  register_vicreg(m);
 }
 }  // namespace sdx_bind

@@ -116,6 +116,30 @@ hipError_t launch_bt_loss_grad(float* C, int D, float lam, double n_total, float
 hipError_t launch_bt_bwd(const float* z1, const float* z2, const float* G, const float* stats, const float* r,
                          const float* g, int n, int D, double n_total, float* dz1, float* dz2, hipStream_t s);
 
+// ---- VICReg loss (vicreg.hip, vicreg_plan.h): symmetric bf16x3 MFMA covariances ---------
+// z1, z2 [n][D] fp32 (n rows on this rank), sums fp64 [3][D] = (Σz1, Σz2, Σ(z1 − z2)²), mu [2][D],
+// C / G [2][D][D] (symmetric bit for bit), coef [2][D]. n_total: the batch size N of the formulas
+// (= n on one rank). Supported: D = 64·j, 64 <= D <= 8192, n >= 1, N >= 2, n·D < 2^31, 16-byte
+// aligned tensors, weights finite and >= 0; everything else is hipErrorInvalidValue before any launch.
+bool vicreg_supported(long n, long D);
+// 1 launch: the column sums; mu != nullptr also finalises them with n_total
+hipError_t launch_vic_colstats(const float* z1, const float* z2, int n, int D, double* sums, float* mu,
+                               double n_total, hipStream_t s);
+// 1 launch: mu from (all-reduced) sums
+hipError_t launch_vic_stats_finalize(const double* sums, int D, double n_total, float* mu, hipStream_t s);
+// 1 launch: C_v = x̄_vᵀ·x̄_v / (n_total − 1) over this rank's rows, both views, upper tiles mirrored
+hipError_t launch_vic_cov(const float* z1, const float* z2, const float* mu, int n, int D, double n_total, float* C,
+                          hipStream_t s);
+// 2 launches: C -> G in place, coef, terms [3] = (L_sim, L_std, L_cov) and loss (device scalars);
+// parts: 2·(2·D/8) doubles of workspace
+hipError_t launch_vic_loss_grad(float* C, const double* sums, int D, double sim_w, double std_w, double cov_w,
+                                float eps, double n_total, float* loss, float* terms, float* coef, double* parts,
+                                hipStream_t s);
+// 1 launch: dz1, dz2 [n][D]; g: the upstream scalar gradient in device memory
+hipError_t launch_vic_bwd(const float* z1, const float* z2, const float* G, const float* mu, const float* coef,
+                          const float* g, int n, int D, double sim_w, double n_total, float* dz1, float* dz2,
+                          hipStream_t s);
+
 // ---- linear-probe sweep: G classifiers on one feature batch (linear_ce_sweep.hip) ----
 // W [G][C][K], bias [G][C], buffers alike, logits / dz [G][B][C], rowstat [G][B][3], stats [G][3].
 // Supported: 1 <= G <= 16, K = 64·2^j <= 2048, 1 <= C <= 1024, B >= 1, G·B·C, B·K and G·C·K

@@ -16,6 +16,8 @@ Additions (new flags only; no reference flag changes meaning):
 ``--knn_freq`` / ``--knn`` with ``--knn_k`` / ``--knn_t`` (weighted k-NN monitor, engine/knn.py),
 ``--blur_p`` / ``--blur_kernel`` / ``--blur_sigma`` (Gaussian-blur augmentation, data/augment.py),
 ``--method BarlowTwins`` with ``--bt_lambda`` (negative-free pretraining objective, losses/barlow.py),
+``--method VICReg`` with ``--vic_sim`` / ``--vic_std`` / ``--vic_cov`` (variance-invariance-covariance
+objective, losses/vicreg.py),
 ``--val_folder`` / ``--resize`` (ImageFolder evaluation: Resize + CenterCrop on the GPU; the linear
 probe also takes ``--dataset path`` with ``--size`` / ``--mean`` / ``--std``),
 ``--sweep_lr`` / ``--sweep_wd`` (linear probe: one classifier per (lr, wd) pair on one encoder pass),
@@ -159,7 +161,7 @@ def pretrain_parser() -> argparse.ArgumentParser:
     p.add_argument("--data_folder", type=str, default=None, help="path to custom dataset")
     p.add_argument("--size", type=int, default=32, help="parameter for RandomResizedCrop")
     # method / temperature (main_supcon.py:59-63)
-    p.add_argument("--method", type=str, default="SimCLR", choices=["SupCon", "SimCLR", "BarlowTwins"])
+    p.add_argument("--method", type=str, default="SimCLR", choices=["SupCon", "SimCLR", "BarlowTwins", "VICReg"])
     p.add_argument("--temp", type=float, default=0.5, help="temperature for loss function")
     # other (main_supcon.py:66-88)
     p.add_argument("--cosine", action="store_true", help="using cosine annealing")
@@ -203,11 +205,15 @@ def pretrain_parser() -> argparse.ArgumentParser:
     g.add_argument("--bt_lambda", type=float, default=argparse.SUPPRESS, metavar="L",
                    help="--method BarlowTwins: weight of the off-diagonal term of the cross-correlation loss; "
                         "default 0.0051")
+    for name, what in (("sim", "invariance"), ("std", "variance"), ("cov", "covariance")):
+        g.add_argument(f"--vic_{name}", type=float, default=argparse.SUPPRESS, metavar="W",
+                       help=f"--method VICReg: weight of the {what} term; default {VIC_WEIGHTS[name]:g}")
     _add_common_new_flags(p)
     return p
 
 
 BT_LAMBDA = 0.0051
+VIC_WEIGHTS = {"sim": 25.0, "std": 25.0, "cov": 1.0}
 
 
 def _finish_common(opt, prefix_dirs: bool):
@@ -260,6 +266,12 @@ def parse_pretrain(argv: Optional[Sequence[str]] = None, make_dirs: bool = True,
             raise ValueError("--bt_lambda must be finite and >= 0")
     elif hasattr(opt, "bt_lambda"):
         raise ValueError("--bt_lambda needs --method BarlowTwins")
+    for name in VIC_WEIGHTS:
+        if opt.method == "VICReg":
+            if not 0.0 <= getattr(opt, "vic_" + name, VIC_WEIGHTS[name]) < math.inf:
+                raise ValueError(f"--vic_{name} must be finite and >= 0")
+        elif hasattr(opt, "vic_" + name):
+            raise ValueError(f"--vic_{name} needs --method VICReg")
     rank, local_rank, world = env_rank_info(opt.local_rank)
     opt.rank, opt.local_rank = rank, local_rank
     if opt.ngpu is None:

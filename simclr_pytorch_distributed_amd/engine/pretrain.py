@@ -1,4 +1,4 @@
-"""Pretraining engine (SimCLR / SupCon / Barlow Twins) — replaces main_supcon.py:155-406.
+"""Pretraining engine (SimCLR / SupCon / Barlow Twins / VICReg) — replaces main_supcon.py:155-406.
 
 Per step (reference hot loop: main_supcon.py:253-349):
 
@@ -103,6 +103,12 @@ class PretrainEngine(TrainEngine):
             from ..losses.barlow import BarlowTwinsLoss
             self.criterion = BarlowTwinsLoss(getattr(opt, "bt_lambda", BT_LAMBDA), backend=loss_backend)
             logging.info("Barlow Twins: --temp, --base_temperature and --contrast_mode are ignored")
+        elif opt.method == "VICReg":
+            from ..config import VIC_WEIGHTS
+            from ..losses.vicreg import VICRegLoss
+            self.criterion = VICRegLoss(*(getattr(opt, "vic_" + k, v) for k, v in VIC_WEIGHTS.items()),
+                                        backend=loss_backend)
+            logging.info("VICReg: --temp, --base_temperature and --contrast_mode are ignored")
         else:
             self.criterion = DistributedContrastiveLoss(opt.method, opt.temp, opt.base_temperature,
                                                         opt.contrast_mode, backend=loss_backend)

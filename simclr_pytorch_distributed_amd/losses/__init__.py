@@ -1,1 +1,2 @@
 from .barlow import BarlowTwinsLoss, barlow_reference  # noqa: F401
+from .vicreg import VICRegLoss, vicreg_reference  # noqa: F401
