@@ -3,46 +3,20 @@
 // barlow_fwd / barlow_bwd are what the autograd node calls on one rank; the forward stages are
 // also ops of their own, between which a multi-rank run all-reduces the column sums and C.
 #include "barlow_plan.h"
-#include "conv_internal.h"
 #include "launchers.h"
 #include "ops_decl.h"
+#include "twoview_checks.h"
 
 namespace sdx_bind {
 namespace {
 
 namespace bp = sdx_barlow;
 
-void check_f32(const torch::Tensor& t, const char* name) {
-  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat && t.is_contiguous(), name,
-              " must be a contiguous fp32 GPU tensor");
-}
-
-// -> (n, D) of the two views
-std::pair<int64_t, int64_t> check_views(const torch::Tensor& z1, const torch::Tensor& z2, double n_total) {
-  check_f32(z1, "z1");
-  check_f32(z2, "z2");
-  TORCH_CHECK(z1.dim() == 2 && z1.sizes() == z2.sizes() && z1.device() == z2.device(),
-              "barlow: z1 and z2 must be [N][D] tensors of equal shape on one device");
-  const int64_t n = z1.size(0), D = z1.size(1);
-  TORCH_CHECK(D % 64 == 0 && D >= bp::kMinD && D <= bp::kMaxD, "barlow: D = 64·j with 64 <= D <= ", bp::kMaxD);
-  TORCH_CHECK(n >= 1 && n_total >= 2 && n_total >= (double)n && n_total < (double)(1 << 24),
-              "barlow: N >= 2 rows (at least this rank's)");
-  TORCH_CHECK(bp::supported(n, D), "barlow: sizes");
-  return {n, D};
-}
-
-void check_vec(const torch::Tensor& t, int64_t rows, int64_t D, const torch::Tensor& like, const char* name) {
-  check_f32(t, name);
-  TORCH_CHECK(t.numel() == rows * D && t.device() == like.device(), name, ": ", rows, " x D fp32 on the views' device");
-}
-
-double total(const torch::Tensor& z1, int64_t n_total) { return n_total > 0 ? (double)n_total : (double)z1.size(0); }
-
 // sums fp64 [2][2][D] = per view (Σz, Σz²); finalize: also stats [2][2][D] = per view (μ, rstd)
 std::vector<torch::Tensor> barlow_colstats(torch::Tensor z1, torch::Tensor z2, double eps, bool finalize,
                                            int64_t n_total) {
   const double nt = total(z1, n_total);
-  auto [n, D] = check_views(z1, z2, finalize ? nt : 2.0 + (double)z1.size(0));
+  auto [n, D] = check_views("barlow", z1, z2, finalize ? nt : 2.0 + (double)z1.size(0));
   c10::DeviceGuard dg(z1.device());
   auto sums = torch::empty({2, 2, D}, z1.options().dtype(at::kDouble));
   torch::Tensor stats;
@@ -71,8 +45,8 @@ torch::Tensor barlow_stats_finalize(torch::Tensor sums, int64_t n_total, double 
 
 torch::Tensor barlow_xcorr(torch::Tensor z1, torch::Tensor z2, torch::Tensor stats, int64_t n_total) {
   const double nt = total(z1, n_total);
-  auto [n, D] = check_views(z1, z2, nt);
-  check_vec(stats, 4, D, z1, "stats");
+  auto [n, D] = check_views("barlow", z1, z2, nt);
+  check_vec(stats, 4 * D, z1, "stats");
   c10::DeviceGuard dg(z1.device());
   auto C = torch::empty({D, D}, z1.options());
   check_hip(launch_bt_xcorr(z1.data_ptr<float>(), z2.data_ptr<float>(), stats.data_ptr<float>(), (int)n, (int)D, nt,
@@ -113,12 +87,11 @@ std::vector<torch::Tensor> barlow_fwd(torch::Tensor z1, torch::Tensor z2, double
 std::vector<torch::Tensor> barlow_bwd(torch::Tensor z1, torch::Tensor z2, torch::Tensor G, torch::Tensor stats,
                                       torch::Tensor r, torch::Tensor g, int64_t n_total) {
   const double nt = total(z1, n_total);
-  auto [n, D] = check_views(z1, z2, nt);
-  check_vec(G, D, D, z1, "G");
-  check_vec(stats, 4, D, z1, "stats");
-  check_vec(r, 2, D, z1, "r");
-  check_f32(g, "g");
-  TORCH_CHECK(g.numel() == 1 && g.device() == z1.device(), "g: one fp32 element on the views' device");
+  auto [n, D] = check_views("barlow", z1, z2, nt);
+  check_vec(G, D * D, z1, "G");
+  check_vec(stats, 4 * D, z1, "stats");
+  check_vec(r, 2 * D, z1, "r");
+  check_g(g, z1);
   c10::DeviceGuard dg(z1.device());
   auto dz1 = torch::empty_like(z1), dz2 = torch::empty_like(z2);
   check_hip(launch_bt_bwd(z1.data_ptr<float>(), z2.data_ptr<float>(), G.data_ptr<float>(), stats.data_ptr<float>(),

@@ -3,39 +3,15 @@
 // (ops/vicreg.py, losses/vicreg.py). vicreg_fwd / vicreg_bwd are what the autograd node calls on one
 // rank; the forward stages are also ops of their own, between which a multi-rank run all-reduces
 // the column sums and C.
-#include "conv_internal.h"
 #include "launchers.h"
 #include "ops_decl.h"
+#include "twoview_checks.h"
 #include "vicreg_plan.h"
 
 namespace sdx_bind {
 namespace {
 
 namespace vp = sdx_vicreg;
-
-void check_f32(const torch::Tensor& t, const char* name) {
-  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat && t.is_contiguous(), name,
-              " must be a contiguous fp32 GPU tensor");
-}
-
-// -> (n, D) of the two views
-std::pair<int64_t, int64_t> check_views(const torch::Tensor& z1, const torch::Tensor& z2, double n_total) {
-  check_f32(z1, "z1");
-  check_f32(z2, "z2");
-  TORCH_CHECK(z1.dim() == 2 && z1.sizes() == z2.sizes() && z1.device() == z2.device(),
-              "vicreg: z1 and z2 must be [N][D] tensors of equal shape on one device");
-  const int64_t n = z1.size(0), D = z1.size(1);
-  TORCH_CHECK(D % 64 == 0 && D >= vp::kMinD && D <= vp::kMaxD, "vicreg: D = 64·j with 64 <= D <= ", vp::kMaxD);
-  TORCH_CHECK(n >= 1 && n_total >= 2 && n_total >= (double)n && n_total < (double)(1 << 24),
-              "vicreg: N >= 2 rows (at least this rank's)");
-  TORCH_CHECK(vp::supported(n, D), "vicreg: sizes");
-  return {n, D};
-}
-
-void check_vec(const torch::Tensor& t, int64_t elems, const torch::Tensor& like, const char* name) {
-  check_f32(t, name);
-  TORCH_CHECK(t.numel() == elems && t.device() == like.device(), name, ": ", elems, " fp32 elements on the views' device");
-}
 
 void check_sums(const torch::Tensor& sums, int64_t D, const char* what) {
   TORCH_CHECK(sums.is_cuda() && sums.scalar_type() == at::kDouble && sums.is_contiguous() && sums.dim() == 2 &&
@@ -48,12 +24,10 @@ void check_weights(double sim, double stdw, double cov, double eps) {
   TORCH_CHECK(ok(sim) && ok(stdw) && ok(cov) && ok(eps), "vicreg: the weights and eps must be finite and >= 0");
 }
 
-double total(const torch::Tensor& z1, int64_t n_total) { return n_total > 0 ? (double)n_total : (double)z1.size(0); }
-
 // sums fp64 [3][D] = (Σz1, Σz2, Σ(z1 − z2)²); finalize: also mu [2][D]
 std::vector<torch::Tensor> vicreg_colstats(torch::Tensor z1, torch::Tensor z2, bool finalize, int64_t n_total) {
   const double nt = total(z1, n_total);
-  auto [n, D] = check_views(z1, z2, finalize ? nt : 2.0 + (double)z1.size(0));
+  auto [n, D] = check_views("vicreg", z1, z2, finalize ? nt : 2.0 + (double)z1.size(0));
   c10::DeviceGuard dg(z1.device());
   auto sums = torch::empty({3, D}, z1.options().dtype(at::kDouble));
   torch::Tensor mu;
@@ -80,7 +54,7 @@ torch::Tensor vicreg_stats_finalize(torch::Tensor sums, int64_t n_total) {
 
 torch::Tensor vicreg_cov(torch::Tensor z1, torch::Tensor z2, torch::Tensor mu, int64_t n_total) {
   const double nt = total(z1, n_total);
-  auto [n, D] = check_views(z1, z2, nt);
+  auto [n, D] = check_views("vicreg", z1, z2, nt);
   check_vec(mu, 2 * D, z1, "mu");
   c10::DeviceGuard dg(z1.device());
   auto C = torch::empty({2, D, D}, z1.options());
@@ -128,12 +102,11 @@ std::vector<torch::Tensor> vicreg_fwd(torch::Tensor z1, torch::Tensor z2, double
 std::vector<torch::Tensor> vicreg_bwd(torch::Tensor z1, torch::Tensor z2, torch::Tensor G, torch::Tensor mu,
                                       torch::Tensor coef, torch::Tensor g, double sim, int64_t n_total) {
   const double nt = total(z1, n_total);
-  auto [n, D] = check_views(z1, z2, nt);
+  auto [n, D] = check_views("vicreg", z1, z2, nt);
   check_vec(G, 2 * D * D, z1, "G");
   check_vec(mu, 2 * D, z1, "mu");
   check_vec(coef, 2 * D, z1, "coef");
-  check_f32(g, "g");
-  TORCH_CHECK(g.numel() == 1 && g.device() == z1.device(), "g: one fp32 element on the views' device");
+  check_g(g, z1);
   check_weights(sim, 0.0, 0.0, 0.0);
   c10::DeviceGuard dg(z1.device());
   auto dz1 = torch::empty_like(z1), dz2 = torch::empty_like(z2);

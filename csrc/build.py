@@ -111,10 +111,11 @@ def build(force: bool = False, jobs: int | None = None, debug: bool = False, ver
     # objects are keyed on the flags and the CONTENT of the source and of every header (an
     # mtime test misses an edit made while that source was compiling)
     hdr_h = hashlib.sha1()
-    hdir = os.path.join(CSRC, "include")
-    for f in sorted(os.listdir(hdir)):
-        with open(os.path.join(hdir, f), "rb") as fh:
-            hdr_h.update(f.encode() + fh.read())
+    hdrs = [os.path.join(CSRC, "include", f) for f in os.listdir(os.path.join(CSRC, "include"))] + \
+        [os.path.join(CSRC, "bindings", f) for f in os.listdir(os.path.join(CSRC, "bindings")) if f.endswith(".h")]
+    for path in sorted(hdrs):
+        with open(path, "rb") as fh:
+            hdr_h.update(os.path.basename(path).encode() + fh.read())
     hdr_digest = hdr_h.hexdigest()
 
     def job(src, flags):

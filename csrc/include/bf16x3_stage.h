@@ -3,7 +3,8 @@
 // centred or standardised per column of z, masked, split into bf16 hi + lo and written as two images
 // of 64-byte rows [output index][32 reduction steps], 16-byte chunks XOR-swizzled. The loaded values
 // stay raw in registers between load() and commit(), so the next chunk's global loads can fly under
-// this chunk's MFMAs. Device code only.
+// this chunk's MFMAs. VICReg's chunk loop (mma_tile) is in loss_gemm.h, Barlow's in barlow.hip. Device
+// code, but for the launchers' operand() builder.
 #pragma once
 #include "common.h"
 
@@ -34,6 +35,14 @@ struct Operand {
   int lim_i, lim_r;
   long si, sr;
 };
+
+// launcher side: element (i, r) at p[i·si + r·sr], i < lim_i, r < lim_r; the statistics where the mode reads them
+inline Operand operand(const float* p, int lim_i, int lim_r, long si, long sr, const float* mu = nullptr,
+                       const float* rstd = nullptr) {
+  Operand o;
+  o.p = p; o.mu = mu; o.rstd = rstd; o.lim_i = lim_i; o.lim_r = lim_r; o.si = si; o.sr = sr;
+  return o;
+}
 
 __device__ __forceinline__ int sw_off(int row, int chunk) {
   return row * kStageRowB + ((chunk ^ ((row >> 1) & 3)) << 4);

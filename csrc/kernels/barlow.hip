@@ -28,8 +28,11 @@
 //                          (kTrans on G). The epilogue recomputes ẑ_v at the accumulator's
 //                          coordinates.
 //                 Tile order: xcd_remap puts consecutive logical tiles on one XCD, and logical
-//                 tiles walk 4 tile rows down before the next tile column, so tiles resident
-//                 together share operand strips in that XCD's L2.
+//                 tiles walk 4 tile rows down before the next tile column (grouped_walk in
+//                 loss_gemm_plan.h), so tiles resident together share operand strips in that XCD's L2.
+//                 The loop is Barlow's own, on one LDS buffer with two barriers per chunk; vicreg.hip's
+//                 double-buffered loop (mma_tile in loss_gemm.h) is not used here: see
+//                 profiles/loss_gemm_share.txt.
 //   bt_loss_grad  one pass over C: a block owns 8 rows, a thread 4 adjacent columns of every
 //                 1024. G overwrites C; r1 = row sums of G⊙C / N, complete in the block (lane
 //                 butterfly, then the 4 waves in order); the block's column sums of G⊙C (8 rows,
@@ -39,21 +42,20 @@
 //
 // Determinism: no atomics, no split reduction; every sum's order is a function of (n, D).
 #include "barlow_plan.h"
-#include "bf16x3_stage.h"
 #include "common.h"
 #include "launchers.h"
+#include "loss_gemm.h"
 
 using namespace sdx;
 
 namespace {
 
 namespace bp = sdx_barlow;
-using namespace sdx_stage;   // Operand, Stager, sw_off, commit8: shared with vicreg.hip
+using namespace sdx_stage;   // Operand, Stager, sw_off, add_row_groups: shared with vicreg.hip
 
 constexpr int KC = bp::kChunk;
-constexpr int TN = bp::kTileN;
+constexpr int TN = bp::kTile;
 constexpr int ROW_B = kStageRowB;   // bytes of one staged bf16 row
-static_assert(KC == kStageChunk, "the staging header's chunk is the plan's");
 
 struct ViewParams {
   Operand a, b;
@@ -167,15 +169,11 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, const ViewParams&
   }
 }
 
-// logical tile -> (tm, tn): kGroupM tile rows down, then the next tile column
+// logical tile -> (tm, tn): grouped_walk (loss_gemm_plan.h) behind the XCD remap
 __device__ __forceinline__ void tile_coords(const GemmParams& p, int bid, int* tm, int* tn) {
-  const int lt = xcd_remap(bid, p.tiles);
-  const int per = bp::kGroupM * p.tiles_n;
-  const int grp = lt / per, in = lt - grp * per;
-  const int first = grp * bp::kGroupM;
-  const int rows = min(p.tiles_m - first, bp::kGroupM);
-  *tn = in / rows;
-  *tm = first + (in - *tn * rows);
+  const bp::TilePos tp = bp::grouped_walk(xcd_remap(bid, p.tiles), p.tiles_m, p.tiles_n, bp::kGroup);
+  *tm = tp.row;
+  *tn = tp.col;
   SDX_DCHECK(*tm < p.tiles_m && *tn < p.tiles_n);
 }
 
@@ -197,6 +195,8 @@ __global__ __launch_bounds__(256) void bt_bwd_kernel(GemmParams p) {
     gemm_tile<bp::kTileMB, kRow, true, kTrans, false, kBwd>(p, p.v[1], tm, tn, stage);
 }
 
+// ---- statistics, loss ------------------------------------------------------------------------
+
 __device__ __forceinline__ void finalize_col(double s, double q, double n_total, float eps, float* mu, float* rstd) {
   const double mean = s / n_total;
   double var = q / n_total - mean * mean;
@@ -208,7 +208,6 @@ __device__ __forceinline__ void finalize_col(double s, double q, double n_total,
 __global__ __launch_bounds__(256) void bt_colstats_kernel(const float* __restrict__ z1, const float* __restrict__ z2,
                                                           int n, int D, double* __restrict__ sums,
                                                           float* __restrict__ stats, double n_total, float eps) {
-  __shared__ double part[2][4][bp::kStatCols];
   const int view = blockIdx.y;
   const float* z = view ? z2 : z1;
   const int cl = threadIdx.x & 63, rg = threadIdx.x >> 6;
@@ -220,16 +219,12 @@ __global__ __launch_bounds__(256) void bt_colstats_kernel(const float* __restric
     s += x;
     q += x * x;
   }
-  part[0][rg][cl] = s;
-  part[1][rg][cl] = q;
-  __syncthreads();
-  if (rg == 0) {
-    s = ((part[0][0][cl] + part[0][1][cl]) + part[0][2][cl]) + part[0][3][cl];
-    q = ((part[1][0][cl] + part[1][1][cl]) + part[1][2][cl]) + part[1][3][cl];
-    sums[(size_t)(view * 2 + 0) * D + col] = s;
-    sums[(size_t)(view * 2 + 1) * D + col] = q;
+  double sq[2] = {s, q};
+  if (add_row_groups(sq)) {
+    sums[(size_t)(view * 2 + 0) * D + col] = sq[0];
+    sums[(size_t)(view * 2 + 1) * D + col] = sq[1];
     if (stats != nullptr)
-      finalize_col(s, q, n_total, eps, stats + (size_t)(view * 2 + 0) * D + col,
+      finalize_col(sq[0], sq[1], n_total, eps, stats + (size_t)(view * 2 + 0) * D + col,
                    stats + (size_t)(view * 2 + 1) * D + col);
   }
 }
@@ -242,12 +237,6 @@ __global__ __launch_bounds__(256) void bt_stats_finalize_kernel(const double* __
   const int view = e / D, col = e - view * D;
   finalize_col(sums[(size_t)(view * 2 + 0) * D + col], sums[(size_t)(view * 2 + 1) * D + col], n_total, eps,
                stats + (size_t)(view * 2 + 0) * D + col, stats + (size_t)(view * 2 + 1) * D + col);
-}
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
 }
 
 __global__ __launch_bounds__(256) void bt_loss_grad_kernel(float* __restrict__ C, int D, float lam, float n_total,
@@ -321,14 +310,6 @@ __global__ __launch_bounds__(256) void bt_loss_finish_kernel(const float* __rest
   r2[j] = (float)(s / n_total);
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-Operand operand(const float* p, const float* mu, const float* rstd, int lim_i, int lim_r, long si, long sr) {
-  Operand o;
-  o.p = p; o.mu = mu; o.rstd = rstd; o.lim_i = lim_i; o.lim_r = lim_r; o.si = si; o.sr = sr;
-  return o;
-}
-
 }  // namespace
 
 bool barlow_supported(long n, long D) { return bp::supported(n, D); }
@@ -362,8 +343,8 @@ hipError_t launch_bt_xcorr(const float* z1, const float* z2, const float* stats,
   if (!(n_total >= n)) return hipErrorInvalidValue;
   GemmParams p = {};
   // element (i = column of z, r = batch row) at z[r·D + i]
-  p.v[0].a = operand(z1, stats, stats + D, D, n, 1, D);
-  p.v[0].b = operand(z2, stats + 2 * (size_t)D, stats + 3 * (size_t)D, D, n, 1, D);
+  p.v[0].a = operand(z1, D, n, 1, D, stats, stats + D);
+  p.v[0].b = operand(z2, D, n, 1, D, stats + 2 * (size_t)D, stats + 3 * (size_t)D);
   p.v[0].out = C;
   p.M = D; p.N = D; p.chunks = pl.x_chunks;
   p.tiles_m = pl.x_tiles_m; p.tiles_n = pl.x_tiles_n; p.tiles = pl.x_tiles;
@@ -379,7 +360,7 @@ hipError_t launch_bt_loss_grad(float* C, int D, float lam, double n_total, float
   if (!bp::make_plan(1, D, &pl) || C == nullptr || r == nullptr || loss == nullptr || r2_part == nullptr ||
       loss_part == nullptr)
     return hipErrorInvalidValue;
-  if (!aligned16(C) || !aligned16(r2_part) || !(n_total >= 1)) return hipErrorInvalidValue;
+  if (!bp::aligned16(C) || !bp::aligned16(r2_part) || !(n_total >= 1)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(bt_loss_grad_kernel, dim3(pl.loss_blocks), dim3(256), 0, s, C, D, lam, (float)n_total, r, r2_part,
                      loss_part);
   SDX_LAUNCH_CHECK();
@@ -395,7 +376,7 @@ hipError_t launch_bt_bwd(const float* z1, const float* z2, const float* G, const
   if (!bp::make_plan(n, D, &pl) || z1 == nullptr || z2 == nullptr || G == nullptr || stats == nullptr ||
       r == nullptr || g == nullptr || dz1 == nullptr || dz2 == nullptr)
     return hipErrorInvalidValue;
-  if (!aligned16(z1) || !aligned16(z2) || !aligned16(G) || !aligned16(stats) || !(n_total >= n))
+  if (!bp::aligned16(z1) || !bp::aligned16(z2) || !bp::aligned16(G) || !bp::aligned16(stats) || !(n_total >= n))
     return hipErrorInvalidValue;
   const float* mu1 = stats;
   const float* rs1 = stats + D;
@@ -403,12 +384,12 @@ hipError_t launch_bt_bwd(const float* z1, const float* z2, const float* G, const
   const float* rs2 = stats + 3 * (size_t)D;
   GemmParams p = {};
   // view 1: A = ẑ2 [n][k], B[d][k] = G[d][k]
-  p.v[0].a = operand(z2, mu2, rs2, n, D, D, 1);
-  p.v[0].b = operand(G, nullptr, nullptr, D, D, D, 1);
+  p.v[0].a = operand(z2, n, D, D, 1, mu2, rs2);
+  p.v[0].b = operand(G, D, D, D, 1);
   p.v[0].z = z1; p.v[0].mu = mu1; p.v[0].rstd = rs1; p.v[0].r = r; p.v[0].out = dz1;
   // view 2: A = ẑ1 [n][k], B[d][k] = G[k][d]
-  p.v[1].a = operand(z1, mu1, rs1, n, D, D, 1);
-  p.v[1].b = operand(G, nullptr, nullptr, D, D, 1, D);
+  p.v[1].a = operand(z1, n, D, D, 1, mu1, rs1);
+  p.v[1].b = operand(G, D, D, 1, D);
   p.v[1].z = z2; p.v[1].mu = mu2; p.v[1].rstd = rs2; p.v[1].r = r + D; p.v[1].out = dz2;
   p.M = n; p.N = D; p.chunks = pl.b_chunks;
   p.tiles_m = pl.b_tiles_m; p.tiles_n = pl.b_tiles_n; p.tiles = pl.b_tiles;

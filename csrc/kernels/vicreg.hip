@@ -1,7 +1,9 @@
 // VICReg loss for gfx950 (--method VICReg): the two D x D auto-covariances of the column-centred
 // projections, the variance hinge and covariance penalty read off them, and the backward, on
 // v_mfma_f32_16x16x32_bf16 with fp32 operands split into bf16 hi + lo (a product is hi·hi + hi·lo +
-// lo·hi, three MFMAs, the lo·lo term dropped; staging shared with barlow.hip in bf16x3_stage.h).
+// lo·hi, three MFMAs, the lo·lo term dropped). The staging (bf16x3_stage.h), the column-statistics
+// sum (loss_gemm.h) and the tile map grouped_walk (loss_gemm_plan.h, with tri_fold) are shared with barlow.hip;
+// the tile loop mma_tile (loss_gemm.h) is used here alone.
 // fp32 in, fp32 out.
 //
 //   vic_colstats   per-column Σz1, Σz2 and Σ(z1 − z2)² in fp64 ([3][D]): a block owns 64 columns of
@@ -12,7 +14,7 @@
 //   vic_cov        C_v = x̄_vᵀ·x̄_v / (N − 1), both views in one launch. C_v is symmetric, so a
 //                  workgroup (4 waves, 2 x 2) owns one 128 x 128 tile (ti, tj) with ti <= tj only:
 //                  T(T + 1)/2 tiles per view instead of T². The triangle is folded into a rectangle
-//                  (vicreg_plan.h) that is walked 4 rows down before the next column, and xcd_remap
+//                  (tri_fold) that is walked 4 rows down before the next column (grouped_walk), and xcd_remap
 //                  puts consecutive logical tiles on one XCD: tiles resident together share operand
 //                  strips in that XCD's L2. The reduction (the batch) goes through LDS in 32-row
 //                  chunks, ascending, never split; lanes run along the columns (kTrans) and an element
@@ -42,9 +44,9 @@
 //                  and z_v − z_other at the accumulator's coordinates; g is a device scalar.
 //
 // Determinism: no atomics, no split reduction; every sum's order is a function of (n, D).
-#include "bf16x3_stage.h"
 #include "common.h"
 #include "launchers.h"
+#include "loss_gemm.h"
 #include "vicreg_plan.h"
 
 using namespace sdx;
@@ -52,92 +54,10 @@ using namespace sdx;
 namespace {
 
 namespace vp = sdx_vicreg;
-using namespace sdx_stage;
+using namespace sdx_stage;   // Operand, Stager, mma_tile, add_row_groups
 
 constexpr int TN = vp::kTile;
 constexpr int ROW_B = kStageRowB;
-static_assert(vp::kChunk == kStageChunk, "the staging header's chunk is the plan's");
-
-// TM x 128 tile at (m0, n0): acc[t][u][r] = Σ_k a[m0 + wm·TM/2 + 16t + 4h + r][k]·b[n0 + 64·wn + 16u + c][k].
-// `stage` holds two buffers of (A hi, A lo, B hi, B lo). DIAG: b is a, staged once. skip: this wave
-// stages and synchronises but issues no MFMAs.
-template <int TM, int MA, int SA, int MB, int SB, bool DIAG>
-__device__ __forceinline__ void mma_tile(const Operand& a, const Operand& b, int m0, int n0, int chunks, bool skip,
-                                         unsigned char* stage, f32x4 (&acc)[TM / 32][4]) {
-  static_assert(!DIAG || TM == TN, "a diagonal tile is square");
-  constexpr int MT = TM / 32;
-  constexpr int A_B = 2 * TM * ROW_B;                       // bytes of A's two images
-  constexpr int BUF = A_B + (DIAG ? 0 : 2 * TN * ROW_B);    // one buffer
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wv = tid >> 6;
-  const int wm = wv >> 1, wn = wv & 1;
-  const int h = lane >> 4;   // 16-lane group: reduction sub-block of the fragments, row group of the accumulator
-  const int c = lane & 15;   // fragment row / accumulator column
-
-  Stager<MA, SA, TM> sa;
-  Stager<MB, SB, TN> sb;
-  sa.init(a, m0, tid);
-  sa.load(a, 0);
-  if constexpr (!DIAG) {
-    sb.init(b, n0, tid);
-    sb.load(b, 0);
-  }
-#pragma unroll
-  for (int t = 0; t < MT; ++t)
-#pragma unroll
-    for (int u = 0; u < 4; ++u) acc[t][u] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  sa.commit(a, 0, stage, stage + TM * ROW_B);
-  if constexpr (!DIAG) sb.commit(b, 0, stage + A_B, stage + A_B + TN * ROW_B);
-
-  for (int kc = 0; kc < chunks; ++kc) {
-    unsigned char* cur = stage + (kc & 1) * BUF;
-    unsigned char* nxt = stage + ((kc + 1) & 1) * BUF;
-    // chunk kc is visible, and every wave is done reading the buffer that chunk kc + 1 goes to
-    __syncthreads();
-    const bool more = kc + 1 < chunks;
-    if (more) {   // the next chunk's loads fly under this chunk's MFMAs
-      sa.load(a, (kc + 1) * kStageChunk);
-      if constexpr (!DIAG) sb.load(b, (kc + 1) * kStageChunk);
-    }
-    if (!skip) {
-      const unsigned char* a_hi = cur;
-      const unsigned char* a_lo = cur + TM * ROW_B;
-      const unsigned char* b_hi = DIAG ? a_hi : cur + A_B;
-      const unsigned char* b_lo = DIAG ? a_lo : cur + A_B + TN * ROW_B;
-      bf16x8 o_hi[4], o_lo[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int boff = sw_off(wn * 64 + 16 * u + c, h);
-        o_hi[u] = *reinterpret_cast<const bf16x8*>(b_hi + boff);
-        o_lo[u] = *reinterpret_cast<const bf16x8*>(b_lo + boff);
-      }
-#pragma unroll
-      for (int t = 0; t < MT; ++t) {
-        const int aoff = sw_off(wm * (TM / 2) + 16 * t + c, h);
-        const bf16x8 f_hi = *reinterpret_cast<const bf16x8*>(a_hi + aoff);
-        const bf16x8 f_lo = *reinterpret_cast<const bf16x8*>(a_lo + aoff);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          acc[t][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f_hi, o_hi[u], acc[t][u], 0, 0, 0);
-          acc[t][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f_hi, o_lo[u], acc[t][u], 0, 0, 0);
-          acc[t][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f_lo, o_hi[u], acc[t][u], 0, 0, 0);
-        }
-      }
-    }
-    if (more) {
-      sa.commit(a, (kc + 1) * kStageChunk, nxt, nxt + TM * ROW_B);
-      if constexpr (!DIAG) sb.commit(b, (kc + 1) * kStageChunk, nxt + A_B, nxt + A_B + TN * ROW_B);
-    }
-  }
-}
-
-Operand operand(const float* p, const float* mu, int lim_i, int lim_r, long si, long sr) {
-  Operand o;
-  o.p = p; o.mu = mu; o.rstd = nullptr; o.lim_i = lim_i; o.lim_r = lim_r; o.si = si; o.sr = sr;
-  return o;
-}
 
 // ---- vic_cov -----------------------------------------------------------------------------
 
@@ -148,32 +68,15 @@ struct CovParams {
   float nm1;      // N − 1
 };
 
-// logical tile of one view -> (ti, tj), ti <= tj: kGroup rows of the folded rectangle down, then
-// the next column; rectangle row r is tile row r followed by tile row T − r − [T even]
-__device__ __forceinline__ void tri_coords(const CovParams& p, int lt, int* ti, int* tj) {
-  const int per = vp::kGroup * p.fold_w;
-  const int grp = lt / per, in = lt - grp * per;
-  const int first = grp * vp::kGroup;
-  const int rows = min(p.fold_h - first, vp::kGroup);
-  const int col = in / rows;
-  const int r = first + (in - col * rows);
-  const int cut = p.T - r;   // tiles of tile row r
-  if (col < cut) {
-    *ti = r;
-    *tj = r + col;
-  } else {
-    *ti = cut - 1 + (p.T & 1);
-    *tj = *ti + (col - cut);
-  }
-  SDX_DCHECK(*ti >= 0 && *ti <= *tj && *tj < p.T);
-}
-
 __global__ __launch_bounds__(256) void vic_cov_kernel(CovParams p) {
   __shared__ __attribute__((aligned(16))) unsigned char stage[2 * 2 * (TN + TN) * ROW_B];   // 64 KiB
   const int lt = xcd_remap(blockIdx.x, 2 * p.tiles);
   const int view = lt >= p.tiles ? 1 : 0;
-  int ti, tj;
-  tri_coords(p, lt - view * p.tiles, &ti, &tj);
+  // logical tile of one view -> the folded rectangle, walked in groups -> (ti, tj), ti <= tj
+  const vp::TilePos rc = vp::grouped_walk(lt - view * p.tiles, p.fold_h, p.fold_w, vp::kGroup);
+  const vp::TilePos tt = vp::tri_fold(rc.row, rc.col, p.T);
+  const int ti = tt.row, tj = tt.col;
+  SDX_DCHECK(ti >= 0 && ti <= tj && tj < p.T);
   const Operand& x = p.x[view];
   const int D = p.D;
   float* C = p.C + (size_t)view * D * D;
@@ -246,18 +149,12 @@ __global__ __launch_bounds__(256) void vic_bwd_kernel(BwdParams p) {
   __shared__ __attribute__((aligned(16))) unsigned char stage[2 * 2 * (TM + TN) * ROW_B];   // 48 KiB
   const int view = (int)blockIdx.x >= p.tiles ? 1 : 0;
   const BwdView& bv = p.v[view];
-  // logical tile -> (tm, tn): kGroup tile rows down, then the next tile column
-  const int lt = xcd_remap((int)blockIdx.x - view * p.tiles, p.tiles);
-  const int per = vp::kGroup * p.tiles_n;
-  const int grp = lt / per, in = lt - grp * per;
-  const int first = grp * vp::kGroup;
-  const int rows = min(p.tiles_m - first, vp::kGroup);
-  const int tn = in / rows;
-  const int tm = first + (in - tn * rows);
-  SDX_DCHECK(tm < p.tiles_m && tn < p.tiles_n);
+  const vp::TilePos tp = vp::grouped_walk(xcd_remap((int)blockIdx.x - view * p.tiles, p.tiles), p.tiles_m,
+                                          p.tiles_n, vp::kGroup);
+  SDX_DCHECK(tp.row < p.tiles_m && tp.col < p.tiles_n);
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int wm = wv >> 1, wn = wv & 1, h = lane >> 4, c = lane & 15;
-  const int m0 = tm * TM, n0 = tn * TN;
+  const int m0 = tp.row * TM, n0 = tp.col * TN;
   f32x4 acc[TM / 32][4];
   mma_tile<TM, kRow, kCentre, kRow, kRaw, false>(bv.a, bv.b, m0, n0, p.chunks, false, stage, acc);
   const float go = p.g[0];
@@ -285,7 +182,6 @@ __global__ __launch_bounds__(256) void vic_bwd_kernel(BwdParams p) {
 __global__ __launch_bounds__(256) void vic_colstats_kernel(const float* __restrict__ z1, const float* __restrict__ z2,
                                                            int n, int D, double* __restrict__ sums,
                                                            float* __restrict__ mu, double n_total) {
-  __shared__ double part[3][4][vp::kStatCols];
   const int cl = threadIdx.x & 63, rg = threadIdx.x >> 6;
   const int col = blockIdx.x * vp::kStatCols + cl;
   double s1 = 0.0, s2 = 0.0, q = 0.0;
@@ -297,20 +193,14 @@ __global__ __launch_bounds__(256) void vic_colstats_kernel(const float* __restri
     s2 += b;
     q += d * d;
   }
-  part[0][rg][cl] = s1;
-  part[1][rg][cl] = s2;
-  part[2][rg][cl] = q;
-  __syncthreads();
-  if (rg == 0) {
-    s1 = ((part[0][0][cl] + part[0][1][cl]) + part[0][2][cl]) + part[0][3][cl];
-    s2 = ((part[1][0][cl] + part[1][1][cl]) + part[1][2][cl]) + part[1][3][cl];
-    q = ((part[2][0][cl] + part[2][1][cl]) + part[2][2][cl]) + part[2][3][cl];
-    sums[col] = s1;
-    sums[(size_t)D + col] = s2;
-    sums[2 * (size_t)D + col] = q;
+  double s[3] = {s1, s2, q};
+  if (add_row_groups(s)) {
+    sums[col] = s[0];
+    sums[(size_t)D + col] = s[1];
+    sums[2 * (size_t)D + col] = s[2];
     if (mu != nullptr) {
-      mu[col] = (float)(s1 / n_total);
-      mu[(size_t)D + col] = (float)(s2 / n_total);
+      mu[col] = (float)(s[0] / n_total);
+      mu[(size_t)D + col] = (float)(s[1] / n_total);
     }
   }
 }
@@ -319,12 +209,6 @@ __global__ __launch_bounds__(256) void vic_stats_finalize_kernel(const double* _
                                                                  double n_total, float* __restrict__ mu) {
   const int e = blockIdx.x * 256 + threadIdx.x;   // (view, column): rows 0 and 1 of sums
   if (e < 2 * D) mu[e] = (float)(sums[e] / n_total);
-}
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
 }
 
 // scale = 4ν/(D(N − 1)), cf = μ/(2·D·(N − 1))
@@ -407,8 +291,6 @@ __global__ __launch_bounds__(256) void vic_loss_finish_kernel(const double* __re
   loss[0] = (float)(sim_w * l_sim + std_w * l_std + cov_w * l_cov);
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 bool weight_ok(double w) { return w >= 0.0 && w < 1e30; }
 
 }  // namespace
@@ -437,10 +319,10 @@ hipError_t launch_vic_cov(const float* z1, const float* z2, const float* mu, int
   vp::Plan pl;
   if (!vp::make_plan(n, D, &pl) || z1 == nullptr || z2 == nullptr || mu == nullptr || C == nullptr)
     return hipErrorInvalidValue;
-  if (!aligned16(C) || !(n_total >= n) || !(n_total >= 2)) return hipErrorInvalidValue;
+  if (!vp::aligned16(C) || !(n_total >= n) || !(n_total >= 2)) return hipErrorInvalidValue;
   CovParams p = {};
-  p.x[0] = operand(z1, mu, D, n, 1, D);
-  p.x[1] = operand(z2, mu + D, D, n, 1, D);
+  p.x[0] = operand(z1, D, n, 1, D, mu);
+  p.x[1] = operand(z2, D, n, 1, D, mu + D);
   p.C = C;
   p.D = D; p.chunks = pl.c_chunks; p.T = pl.c_t; p.fold_w = pl.c_fold_w; p.fold_h = pl.c_fold_h; p.tiles = pl.c_tiles;
   p.nm1 = (float)(n_total - 1.0);
@@ -456,7 +338,8 @@ hipError_t launch_vic_loss_grad(float* C, const double* sums, int D, double sim_
   if (!vp::make_plan(1, D, &pl) || C == nullptr || sums == nullptr || loss == nullptr || terms == nullptr ||
       coef == nullptr || parts == nullptr)
     return hipErrorInvalidValue;
-  if (!aligned16(C) || !(n_total >= 2) || !weight_ok(sim_w) || !weight_ok(std_w) || !weight_ok(cov_w) || !(eps >= 0.f))
+  if (!vp::aligned16(C) || !(n_total >= 2) || !weight_ok(sim_w) || !weight_ok(std_w) || !weight_ok(cov_w) ||
+      !(eps >= 0.f))
     return hipErrorInvalidValue;
   const double dn = (double)D * (n_total - 1.0);
   double* cov_part = parts;
@@ -477,14 +360,15 @@ hipError_t launch_vic_bwd(const float* z1, const float* z2, const float* G, cons
   if (!vp::make_plan(n, D, &pl) || z1 == nullptr || z2 == nullptr || G == nullptr || mu == nullptr ||
       coef == nullptr || g == nullptr || dz1 == nullptr || dz2 == nullptr)
     return hipErrorInvalidValue;
-  if (!aligned16(z1) || !aligned16(z2) || !aligned16(G) || !aligned16(mu) || !(n_total >= n) || !weight_ok(sim_w))
+  if (!vp::aligned16(z1) || !vp::aligned16(z2) || !vp::aligned16(G) || !vp::aligned16(mu) || !(n_total >= n) ||
+      !weight_ok(sim_w))
     return hipErrorInvalidValue;
   BwdParams p = {};
   const float* zs[2] = {z1, z2};
   float* outs[2] = {dz1, dz2};
   for (int v = 0; v < 2; ++v) {
-    p.v[v].a = operand(zs[v], mu + (size_t)v * D, n, D, D, 1);
-    p.v[v].b = operand(G + (size_t)v * D * D, nullptr, D, D, D, 1);
+    p.v[v].a = operand(zs[v], n, D, D, 1, mu + (size_t)v * D);
+    p.v[v].b = operand(G + (size_t)v * D * D, D, D, D, 1);
     p.v[v].z = zs[v];
     p.v[v].zo = zs[1 - v];
     p.v[v].mu = mu + (size_t)v * D;

@@ -7,24 +7,19 @@ batch (``BatchNorm1d(affine=False)`` in training mode: biased variance, ε = 1e-
 
 * :func:`barlow_reference` — plain torch, any device and dtype: the CPU path, ``--backend torch``
   and the oracle's twin.
-* :class:`BarlowTwinsLoss` — called as ``criterion(feats, labels=None)`` with ``feats``
-  ``[2·B_l][D]`` view-major, as ``DistributedContrastiveLoss`` is. On the GPU it runs the native
-  kernels (ops/barlow.py); ``backend="native"`` raises when they cannot take the call.
+* :class:`BarlowTwinsLoss` — the criterion (losses/twoview.py); on the GPU it runs the native
+  kernels (ops/barlow.py).
 
 With W ranks N is the global batch: the column sums and C are summed over the process group
-(differentiably in the twin). Every rank then holds the same L and returns L / W, so the sum over
-ranks is the global loss and each rank's gradient is the exact gradient of that loss w.r.t. its
-own rows, as the contrastive criterion's.
+(differentiably in the twin).
 """
 from __future__ import annotations
 
-import logging
-from typing import Optional
-
 import torch
-import torch.nn as nn
 
+from ..ops import barlow
 from ..parallel import comm
+from .twoview import TwoViewLoss
 
 
 def barlow_reference(z1: torch.Tensor, z2: torch.Tensor, lambd: float = 0.0051, eps: float = 1e-5) -> torch.Tensor:
@@ -45,41 +40,16 @@ def barlow_reference(z1: torch.Tensor, z2: torch.Tensor, lambd: float = 0.0051, 
     return on + lambd * off
 
 
-class BarlowTwinsLoss(nn.Module):
+class BarlowTwinsLoss(TwoViewLoss):
+    name, ops = "Barlow Twins", barlow
+
     def __init__(self, lambd: float = 0.0051, eps: float = 1e-5, backend: str = "auto"):
-        super().__init__()
-        if backend not in ("auto", "native", "torch"):
-            raise ValueError(f"backend {backend!r}")
+        super().__init__(backend)
         self.lambd = float(lambd)
         self.eps = float(eps)
-        self.backend = backend
-        self._warned = False
 
-    def _use_native(self, z1: torch.Tensor, n_total: int) -> bool:
-        if self.backend == "torch":
-            return False
-        from ..ops import _ext, barlow
-        if self.backend == "native":
-            return True     # ops.barlow raises on what it cannot take: never a silent fall-back
-        if not (z1.is_cuda and z1.dtype == torch.float32 and _ext.available()):
-            return False
-        if not barlow.supported(n_total, z1.shape[1]):
-            if not self._warned:
-                self._warned = True
-                logging.warning(f"Barlow Twins: N={n_total}, D={z1.shape[1]} is outside the native kernels' range "
-                                f"(D = 64·j in [{barlow.MIN_D}, {barlow.MAX_D}]); using the torch loss")
-            return False
-        return True
+    def native(self, z1, z2):
+        return barlow.barlow_loss(z1, z2, self.lambd, self.eps)
 
-    def forward(self, feats: torch.Tensor, labels: Optional[torch.Tensor] = None) -> torch.Tensor:
-        if feats.dim() != 2 or feats.shape[0] % 2:
-            raise ValueError("`feats` must be [2·B][D]: view 1 of every sample, then view 2")
-        b = feats.shape[0] // 2
-        z1, z2 = feats[:b], feats[b:]
-        w = comm.world_size()
-        if self._use_native(z1, b * w):
-            from ..ops import barlow
-            loss = barlow.barlow_loss(z1, z2, self.lambd, self.eps)
-        else:
-            loss = barlow_reference(z1, z2, self.lambd, self.eps)
-        return loss / w if w > 1 else loss
+    def twin(self, z1, z2):
+        return barlow_reference(z1, z2, self.lambd, self.eps)

@@ -12,24 +12,19 @@ For the projections z1, z2 ``[N][D]`` of the two views, with x̄_v = z_v − μ_
 
 * :func:`vicreg_reference` — plain torch, any device and dtype: the CPU path, ``--backend torch``
   and the oracle's twin.
-* :class:`VICRegLoss` — called as ``criterion(feats, labels=None)`` with ``feats`` ``[2·B_l][D]``
-  view-major, as ``DistributedContrastiveLoss`` is. On the GPU it runs the native kernels
-  (ops/vicreg.py); ``backend="native"`` raises when they cannot take the call.
+* :class:`VICRegLoss` — the criterion (losses/twoview.py); on the GPU it runs the native kernels
+  (ops/vicreg.py).
 
 With W ranks N is the global batch: the column sums, the invariance sum and C are summed over the
-process group (differentiably in the twin). Every rank then holds the same L and returns L / W, so
-the sum over ranks is the global loss and each rank's gradient is the exact gradient of that loss
-w.r.t. its own rows, as the contrastive criterion's.
+process group (differentiably in the twin).
 """
 from __future__ import annotations
 
-import logging
-from typing import Optional
-
 import torch
-import torch.nn as nn
 
+from ..ops import vicreg
 from ..parallel import comm
+from .twoview import TwoViewLoss
 
 
 def vicreg_reference(z1: torch.Tensor, z2: torch.Tensor, sim: float = 25.0, std: float = 25.0, cov: float = 1.0,
@@ -49,42 +44,17 @@ def vicreg_reference(z1: torch.Tensor, z2: torch.Tensor, sim: float = 25.0, std:
     return sim * l_sim + std * l_std + cov * l_cov
 
 
-class VICRegLoss(nn.Module):
+class VICRegLoss(TwoViewLoss):
+    name, ops = "VICReg", vicreg
+
     def __init__(self, sim: float = 25.0, std: float = 25.0, cov: float = 1.0, eps: float = 1e-4,
                  backend: str = "auto"):
-        super().__init__()
-        if backend not in ("auto", "native", "torch"):
-            raise ValueError(f"backend {backend!r}")
+        super().__init__(backend)
         self.sim, self.std, self.cov = float(sim), float(std), float(cov)
         self.eps = float(eps)
-        self.backend = backend
-        self._warned = False
 
-    def _use_native(self, z1: torch.Tensor, n_total: int) -> bool:
-        if self.backend == "torch":
-            return False
-        from ..ops import _ext, vicreg
-        if self.backend == "native":
-            return True     # ops.vicreg raises on what it cannot take: never a silent fall-back
-        if not (z1.is_cuda and z1.dtype == torch.float32 and _ext.available()):
-            return False
-        if not vicreg.supported(n_total, z1.shape[1]):
-            if not self._warned:
-                self._warned = True
-                logging.warning(f"VICReg: N={n_total}, D={z1.shape[1]} is outside the native kernels' range "
-                                f"(D = 64·j in [{vicreg.MIN_D}, {vicreg.MAX_D}]); using the torch loss")
-            return False
-        return True
+    def native(self, z1, z2):
+        return vicreg.vicreg_loss(z1, z2, self.sim, self.std, self.cov, self.eps)
 
-    def forward(self, feats: torch.Tensor, labels: Optional[torch.Tensor] = None) -> torch.Tensor:
-        if feats.dim() != 2 or feats.shape[0] % 2:
-            raise ValueError("`feats` must be [2·B][D]: view 1 of every sample, then view 2")
-        b = feats.shape[0] // 2
-        z1, z2 = feats[:b], feats[b:]
-        w = comm.world_size()
-        if self._use_native(z1, b * w):
-            from ..ops import vicreg
-            loss = vicreg.vicreg_loss(z1, z2, self.sim, self.std, self.cov, self.eps)
-        else:
-            loss = vicreg_reference(z1, z2, self.sim, self.std, self.cov, self.eps)
-        return loss / w if w > 1 else loss
+    def twin(self, z1, z2):
+        return vicreg_reference(z1, z2, self.sim, self.std, self.cov, self.eps)

@@ -13,13 +13,7 @@ import torch
 
 from ..parallel import comm
 from . import _ext
-
-MIN_D, MAX_D = 64, 8192
-
-
-def supported(n: int, D: int) -> bool:
-    """Shapes the native kernels take: D = 64·j in [64, 8192], at least 2 rows, n·D < 2^31."""
-    return D % 64 == 0 and MIN_D <= D <= MAX_D and n >= 2 and n * D < 2 ** 31
+from .twoview import MAX_D, MIN_D, check_views, supported  # noqa: F401
 
 
 class _BarlowLoss(torch.autograd.Function):
@@ -55,11 +49,5 @@ class _BarlowLoss(torch.autograd.Function):
 
 def barlow_loss(z1: torch.Tensor, z2: torch.Tensor, lambd: float, eps: float = 1e-5) -> torch.Tensor:
     """Native Barlow Twins loss of fp32 GPU views ``[n][D]``; raises outside :func:`supported`."""
-    if not (z1.is_cuda and z1.dtype == torch.float32 and z2.dtype == torch.float32 and z1.shape == z2.shape
-            and z1.dim() == 2):
-        raise RuntimeError("Barlow Twins native backend needs two fp32 GPU tensors [n][D] of equal shape")
-    n, D = z1.shape[0] * comm.world_size(), z1.shape[1]
-    if not supported(n, D):
-        raise RuntimeError(f"Barlow Twins native backend: unsupported shape N={n}, D={D} "
-                           f"(D = 64·j in [{MIN_D}, {MAX_D}], N >= 2)")
+    check_views("Barlow Twins", z1, z2)
     return _BarlowLoss.apply(z1, z2, float(lambd), float(eps))

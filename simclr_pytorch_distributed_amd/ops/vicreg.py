@@ -14,13 +14,7 @@ import torch
 
 from ..parallel import comm
 from . import _ext
-
-MIN_D, MAX_D = 64, 8192
-
-
-def supported(n: int, D: int) -> bool:
-    """Shapes the native kernels take: D = 64·j in [64, 8192], at least 2 rows, n·D < 2^31."""
-    return D % 64 == 0 and MIN_D <= D <= MAX_D and n >= 2 and n * D < 2 ** 31
+from .twoview import MAX_D, MIN_D, check_views, supported  # noqa: F401
 
 
 class _VICRegLoss(torch.autograd.Function):
@@ -57,11 +51,5 @@ class _VICRegLoss(torch.autograd.Function):
 def vicreg_loss(z1: torch.Tensor, z2: torch.Tensor, sim: float = 25.0, std: float = 25.0, cov: float = 1.0,
                 eps: float = 1e-4) -> torch.Tensor:
     """Native VICReg loss of fp32 GPU views ``[n][D]``; raises outside :func:`supported`."""
-    if not (z1.is_cuda and z1.dtype == torch.float32 and z2.dtype == torch.float32 and z1.shape == z2.shape
-            and z1.dim() == 2):
-        raise RuntimeError("VICReg native backend needs two fp32 GPU tensors [n][D] of equal shape")
-    n, D = z1.shape[0] * comm.world_size(), z1.shape[1]
-    if not supported(n, D):
-        raise RuntimeError(f"VICReg native backend: unsupported shape N={n}, D={D} "
-                           f"(D = 64·j in [{MIN_D}, {MAX_D}], N >= 2)")
+    check_views("VICReg", z1, z2)
     return _VICRegLoss.apply(z1, z2, float(sim), float(std), float(cov), float(eps))

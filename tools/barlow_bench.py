@@ -13,13 +13,13 @@ from __future__ import annotations
 
 import argparse
 import os
-import statistics
 import sys
 
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+from loss_bench_common import interleaved, med, timed  # noqa: E402
 from simclr_pytorch_distributed_amd.losses.barlow import barlow_reference  # noqa: E402
 from simclr_pytorch_distributed_amd.ops import _ext, barlow  # noqa: E402
 
@@ -27,26 +27,11 @@ SHAPES = [(n, d) for n in (256, 1024) for d in (128, 2048, 8192)]
 LAM, EPS = 0.0051, 1e-5
 
 
-def timed(fn, iters):
-    """ms per call of ``iters`` calls between two device events."""
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(iters):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / iters
-
-
 def fwd_bwd(loss_fn, z1, z2):
     def run():
         z1.grad = z2.grad = None
         loss_fn(z1, z2, LAM, EPS).backward()
     return run
-
-
-def med(xs):
-    return statistics.median(xs)
 
 
 def bench_shape(n, d, rounds, iters, emit):
@@ -61,19 +46,11 @@ def bench_shape(n, d, rounds, iters, emit):
     gt = z1.grad.clone()
     native()
     rel = ((z1.grad - gt).abs().max() / gt.abs().max()).item()
-    for _ in range(3):
-        twin()
-        native()
-    ta, tn, tb = [], [], []
-    for _ in range(rounds):
-        ta.append(timed(twin, iters))
-        tn.append(timed(native, iters))
-        tb.append(timed(twin, iters))
-    a, b, nat = med(ta), med(tb), med(tn)
+    a, b, nat, lo, hi = interleaved(twin, native, rounds, iters)
     base = 0.5 * (a + b)
     slower = nat > min(a, b)
     emit(f"N={n:5d} D={d:5d}  twin {a:8.3f} / {b:8.3f} ms (two series)  native {nat:8.3f} ms "
-         f"[{min(tn):.3f} .. {max(tn):.3f}]  twin/native {base / nat:5.2f}x{'  NATIVE SLOWER' if slower else ''}"
+         f"[{lo:.3f} .. {hi:.3f}]  twin/native {base / nat:5.2f}x{'  NATIVE SLOWER' if slower else ''}"
          f"  grad diff/max {rel:.2e}")
     # stages, one op each
     a1, a2 = z1.detach(), z2.detach()

@@ -21,42 +21,18 @@ from __future__ import annotations
 
 import argparse
 import os
-import statistics
 import sys
 
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+from loss_bench_common import interleaved, med, timed  # noqa: E402
 from simclr_pytorch_distributed_amd.losses.vicreg import vicreg_reference  # noqa: E402
 from simclr_pytorch_distributed_amd.ops import _ext, vicreg  # noqa: E402
 
 SHAPES = [(n, d) for n in (256, 1024) for d in (128, 2048, 8192)]
 W, EPS = (25.0, 25.0, 1.0), 1e-4
-
-
-def timed(fn, iters):
-    """ms per call of ``iters`` calls between two device events."""
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(iters):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / iters
-
-
-def interleaved(base, new, rounds, iters):
-    """-> medians (base series 1, base series 2, new) and new's range."""
-    for _ in range(3):
-        base()
-        new()
-    ta, tn, tb = [], [], []
-    for _ in range(rounds):
-        ta.append(timed(base, iters))
-        tn.append(timed(new, iters))
-        tb.append(timed(base, iters))
-    return statistics.median(ta), statistics.median(tb), statistics.median(tn), min(tn), max(tn)
 
 
 def fwd_bwd(loss_fn, z1, z2):
@@ -112,7 +88,7 @@ def bench_shape(n, d, rounds, iters, emit):
     parts = []
     for name, fn in stages.items():
         fn()
-        parts.append(f"{name} {statistics.median([timed(fn, iters) for _ in range(rounds)]) * 1e3:.1f} us")
+        parts.append(f"{name} {med([timed(fn, iters) for _ in range(rounds)]) * 1e3:.1f} us")
     emit(f"    stages: {'  '.join(parts)}   (2·D²·N = {2 * d * d * n / 1e9:.2f} GFLOP per full GEMM, x3 MFMAs each)")
 
 
