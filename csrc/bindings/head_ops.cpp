@@ -16,6 +16,7 @@
 // Numerics: bf16 operands, fp32 accumulation, fp32 biases added to the fp32 accumulators,
 // bf16 hidden activation (as torch autocast), fp32 output features.
 #include "conv_internal.h"
+#include "head_gemm_ops.h"
 #include "launchers.h"
 #include "ops_decl.h"
 
@@ -36,6 +37,10 @@ void check_w(const torch::Tensor& w, int64_t rows, int64_t cols, const char* nam
               " must be a contiguous bf16 GPU tensor of ", rows, "x", cols, " elements");
 }
 
+}  // namespace
+
+// ---- the head's GEMM stages, shared with the BatchNorm head (head_gemm_ops.h) ----
+
 void check_2d(const torch::Tensor& t, at::ScalarType dt, const char* name) {
   TORCH_CHECK(t.is_cuda() && t.scalar_type() == dt && t.dim() == 2 && t.is_contiguous(), name,
               " must be a contiguous 2-D GPU tensor of ", c10::toString(dt));
@@ -53,6 +58,8 @@ const torch::Tensor& const_vec(const torch::Device& dev, int64_t n, float v) {
   return t;
 }
 
+namespace {
+
 // the head's GEMMs have few rows (one per view on this rank): the 64x64 tile is the only
 // one that puts enough blocks on the chip for their long reductions (512 rows, 2048 -> 2048:
 // 22.0 vs 28.6 us auto; 2048 -> 128: 15.5 us, profiles/head_gemm_r5.txt)
@@ -64,6 +71,8 @@ ConvGeom gemm_geom(int64_t rows, int64_t in, int64_t out) {
   // a [rows] x [in] -> [out] GEMM as a 1x1 conv over `rows` single-pixel images
   return conv_geom(rows, 1, 1, in, out, 1, 1, 1, 0);
 }
+
+}  // namespace
 
 // y[rows][out] = x[rows][in] · W[out][in]ᵀ (+ bias) (ReLU); bf16 or fp32 output
 torch::Tensor gemm_fwd(const torch::Tensor& x, const torch::Tensor& w, const torch::Tensor& bias, bool relu,
@@ -115,7 +124,7 @@ void gemm_wgrad(const torch::Tensor& dy, const torch::Tensor& x, torch::Tensor& 
 // masked column sums added into `bias_sink` (the hidden layer's bias gradient)
 // (slab_out: the caller reduces the bias-gradient slab itself, e.g. on another stream)
 torch::Tensor gemm_dgrad(const torch::Tensor& dy, const torch::Tensor& wt, int64_t in, bool out_f32,
-                         const torch::Tensor* relu_ref, torch::Tensor* bias_sink, torch::Tensor* slab_out = nullptr) {
+                         const torch::Tensor* relu_ref, torch::Tensor* bias_sink, torch::Tensor* slab_out) {
   const int64_t rows = dy.size(0), out = dy.size(1);
   check_w(wt, in, out, "Wt");
   TORCH_CHECK(in % 8 == 0, "input features must be a multiple of 8");
@@ -149,6 +158,8 @@ torch::Tensor gemm_dgrad(const torch::Tensor& dy, const torch::Tensor& wt, int64
   else colsum_into(slab, mt, 2, in, *bias_sink);
   return dx;
 }
+
+namespace {
 
 // feat [N][D] fp32|bf16; w1 [O1][D] bf16 (+ b1 fp32); MLP: w2 [O2][O1] bf16 (+ b2).
 // Returns [z fp32 [N][O_last], fb bf16 [N][D], h bf16 [N][O1] (MLP; empty otherwise)].

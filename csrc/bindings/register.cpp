@@ -13,6 +13,7 @@ void register_wprep(pybind11::module& m);
 void register_xgmi(pybind11::module& m);
 void register_comm(pybind11::module& m);
 void register_head(pybind11::module& m);
+void register_head_bn(pybind11::module& m);
 void register_probe(pybind11::module& m);
 void register_knn(pybind11::module& m);
 void register_barlow(pybind11::module& m);
@@ -30,6 +31,7 @@ void register_ops(pybind11::module& m) {
   register_xgmi(m);
   register_comm(m);
   register_head(m);
+  register_head_bn(m);
   register_probe(m);
   register_knn(m);
   register_barlow(m);

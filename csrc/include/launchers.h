@@ -444,3 +444,41 @@ hipError_t launch_xgmi_allreduce(const double* in, double* out, int n, const Xgm
 hipError_t launch_gpu_stall(long long ticks, hipStream_t s);
 hipError_t launch_xgmi_emulate(const double* in, double* out, int n, const XgmiPeers& peers, int world,
                                unsigned epoch, int* err, hipStream_t s);
+
+// ---- BatchNorm projector head (head_bn.hip, head_bn_plan.h) --------------------------
+// One hidden layer Linear(bias=False) -> BatchNorm1d -> ReLU, forward: x [N][K], w [H][K] bf16;
+// yb = bf16(x·wᵀ) and a = bf16(relu(γ·(yb − μ)·rstd + β)) [N][H] bf16; μ, rstd [H] fp32 (biased
+// variance of yb); rmean / rvar updated in place with `momentum` (unbiased variance).
+struct HbnFwdArgs {
+  const uint16_t* x;
+  const uint16_t* w;
+  const float* gamma;
+  const float* beta;
+  float* rmean;
+  float* rvar;
+  uint16_t* yb;
+  uint16_t* a;
+  float* mu;
+  float* rstd;
+  int N, K, H;
+  float momentum, eps;
+};
+// strip: 0 = the plan's strip width, 16 | 32 forces one. hipErrorInvalidValue before any launch
+// outside the plan's range (head_bn_plan.h supported()) or for operands not 16-byte aligned.
+hipError_t launch_hbn_fwd(const HbnFwdArgs& a, int strip, hipStream_t s);
+// ... backward: dy [N][H] bf16 from da and the saved yb, μ, rstd; dβ, dγ ADDED into the sinks;
+// a_out (optional): the layer's activation, recomputed
+struct HbnBwdArgs {
+  const uint16_t* da;
+  const uint16_t* yb;
+  const float* mu;
+  const float* rstd;
+  const float* gamma;
+  const float* beta;
+  float* sink_gamma;
+  float* sink_beta;
+  uint16_t* dy;
+  uint16_t* a_out;
+  int N, H;
+};
+hipError_t launch_hbn_bwd(const HbnBwdArgs& a, hipStream_t s);

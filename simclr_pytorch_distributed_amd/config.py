@@ -18,6 +18,8 @@ Additions (new flags only; no reference flag changes meaning):
 ``--method BarlowTwins`` with ``--bt_lambda`` (negative-free pretraining objective, losses/barlow.py),
 ``--method VICReg`` with ``--vic_sim`` / ``--vic_std`` / ``--vic_cov`` (variance-invariance-covariance
 objective, losses/vicreg.py),
+``--head mlp_bn`` with ``--head_hidden`` / ``--head_layers`` (pretraining only: the BatchNorm projector of
+Barlow Twins / VICReg, models/resnet.py ``bn_projector``, natively on csrc/kernels/head_bn.hip),
 ``--val_folder`` / ``--resize`` (ImageFolder evaluation: Resize + CenterCrop on the GPU; the linear
 probe also takes ``--dataset path`` with ``--size`` / ``--mean`` / ``--std``),
 ``--sweep_lr`` / ``--sweep_wd`` (linear probe: one classifier per (lr, wd) pair on one encoder pass),
@@ -69,7 +71,7 @@ def env_rank_info(cli_local_rank: Optional[int] = None):
     return rank, local_rank, world
 
 
-def _add_common_new_flags(p: argparse.ArgumentParser):
+def _add_common_new_flags(p: argparse.ArgumentParser, heads=("mlp", "linear")):
     g = p.add_argument_group("MI355X framework options (new)")
     g.add_argument("--backend", type=str, default="auto", choices=["auto", "native", "torch"],
                    help="compute path: native gfx950 kernels, stock torch ops, or auto")
@@ -79,7 +81,7 @@ def _add_common_new_flags(p: argparse.ArgumentParser):
     g.add_argument("--synthetic_size", type=int, default=50000)
     g.add_argument("--seed", type=int, default=0)
     g.add_argument("--stem", type=str, default="cifar", choices=["cifar", "imagenet"])
-    g.add_argument("--head", type=str, default="mlp", choices=["mlp", "linear"])
+    g.add_argument("--head", type=str, default="mlp", choices=list(heads))
     g.add_argument("--feat_dim", type=int, default=128)
     g.add_argument("--work_dir", type=str, default="./work_space")
     g.add_argument("--dist_backend", type=str, default="auto", choices=["auto", "nccl", "gloo"])
@@ -208,7 +210,13 @@ def pretrain_parser() -> argparse.ArgumentParser:
     for name, what in (("sim", "invariance"), ("std", "variance"), ("cov", "covariance")):
         g.add_argument(f"--vic_{name}", type=float, default=argparse.SUPPRESS, metavar="W",
                        help=f"--method VICReg: weight of the {what} term; default {VIC_WEIGHTS[name]:g}")
-    _add_common_new_flags(p)
+    g.add_argument("--head_hidden", type=int, default=argparse.SUPPRESS, metavar="H",
+                   help="--head mlp_bn: width of the hidden layers, a multiple of 32; default: the encoder's "
+                        "output width (2048 for resnet50)")
+    g.add_argument("--head_layers", type=int, default=argparse.SUPPRESS, choices=[2, 3], metavar="L",
+                   help="--head mlp_bn: Linear layers of the projector (L - 1 hidden Linear-BatchNorm1d-ReLU "
+                        "layers and the output Linear); default 3")
+    _add_common_new_flags(p, heads=("mlp", "linear", "mlp_bn"))
     return p
 
 
@@ -272,6 +280,17 @@ def parse_pretrain(argv: Optional[Sequence[str]] = None, make_dirs: bool = True,
                 raise ValueError(f"--vic_{name} must be finite and >= 0")
         elif hasattr(opt, "vic_" + name):
             raise ValueError(f"--vic_{name} needs --method VICReg")
+    if opt.head == "mlp_bn":
+        if opt.micro_batch > 0:
+            raise ValueError("--head mlp_bn cannot run with --micro_batch: gradient caching takes the head's rows "
+                             "as independent, and BatchNorm1d couples them")
+        if getattr(opt, "head_hidden", 32) % 32 or getattr(opt, "head_hidden", 32) < 32 or opt.feat_dim % 32 \
+                or opt.feat_dim < 32:
+            raise ValueError("--head mlp_bn needs --head_hidden and --feat_dim to be multiples of 32")
+    else:
+        for name in ("head_hidden", "head_layers"):
+            if hasattr(opt, name):
+                raise ValueError(f"--{name} needs --head mlp_bn")
     rank, local_rank, world = env_rank_info(opt.local_rank)
     opt.rank, opt.local_rank = rank, local_rank
     if opt.ngpu is None:

@@ -106,6 +106,11 @@ class TrainEngine:
                 self._setup_syncbn_comm(opt, dev)
                 if self.syncbn_transport == "none":
                     self.syncbn_transport = "process-group"
+            from ..models.resnet import is_bn_projector
+            if is_bn_projector(getattr(model, "head", None)):
+                # no fused SyncBN for the projector's BatchNorm1d: synchronised torch modules on either backend
+                model.head = torch.nn.SyncBatchNorm.convert_sync_batchnorm(model.head)
+                logging.info("mlp_bn head: SyncBN group: the head runs as torch SyncBatchNorm modules")
         self._setup_more_comm(opt, dev)
         model = model.to(dev)
         if dev.type == "cuda":

@@ -73,7 +73,18 @@ class LinearEngine:
             model = SupConResNet(opt.model, opt.head, opt.feat_dim, opt.stem)
             if opt.ckpt:
                 st = ckpt_mod.load_checkpoint(opt.ckpt)
-                ckpt_mod.load_model_state(model, st["model"])
+                sd = ckpt_mod.strip_prefix(st["model"])
+                own = model.state_dict()
+                if {k for k in sd if k.startswith("head")} != {k for k in own if k.startswith("head")}:
+                    # another projector than --head builds here (a --head mlp_bn pretraining run):
+                    # the probe reads the encoder only, which must be complete
+                    sd = {k: v for k, v in sd.items() if not k.startswith("head")}
+                    missing, unexpected = ckpt_mod.load_model_state(model, sd, strict=False)
+                    lost = [k for k in missing if not k.startswith("head")]
+                    if lost or unexpected:
+                        raise KeyError(f"state dict mismatch: missing={lost[:5]} unexpected={unexpected[:5]}")
+                else:
+                    ckpt_mod.load_model_state(model, sd)
                 logging.info(f"loaded encoder from {opt.ckpt}")
             else:
                 logging.warning("no --ckpt given: probing a randomly initialised encoder")

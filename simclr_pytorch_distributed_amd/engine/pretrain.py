@@ -46,7 +46,8 @@ _NORM_SIDE = os.environ.get("SDX_NORM_SIDE", "1") != "0"
 class PretrainEngine(TrainEngine):
     def _build_model(self):
         opt = self.opt
-        model = SupConResNet(opt.model, opt.head, opt.feat_dim, opt.stem)
+        model = SupConResNet(opt.model, opt.head, opt.feat_dim, opt.stem, head_hidden=getattr(opt, "head_hidden", 0),
+                             head_layers=getattr(opt, "head_layers", 3))
         if opt.ckpt:
             sd = ckpt_mod.load_checkpoint(opt.ckpt)["model"]
             ckpt_mod.load_model_state(model, sd)

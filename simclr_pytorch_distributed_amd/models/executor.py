@@ -28,7 +28,7 @@ import torch.nn.functional as F
 from ..ops.bn import bn_act, bn_add_act
 from ..ops.conv import conv2d_nhwc
 from ..ops.pool import global_avgpool_nhwc, maxpool_nhwc
-from .resnet import BasicBlock, Bottleneck, ResNet
+from .resnet import BasicBlock, Bottleneck, ResNet, is_bn_projector
 
 INPUT_CHANNELS_PADDED = 8   # NHWC input images carry 3 channels padded to 8 (16-byte rows)
 
@@ -79,6 +79,11 @@ def head_forward(head, feat: torch.Tensor, dtype=torch.bfloat16) -> torch.Tensor
     """Projection head in ``dtype`` with fp32 master weights (networks/resnet_big.py:168-172)."""
     if isinstance(head, torch.nn.Linear):
         return F.linear(feat.to(dtype), head.weight.to(dtype), head.bias.to(dtype)).float()
+    if is_bn_projector(head):      # the modules themselves (BatchNorm1d statistics and buffers), autocast on the GPU
+        if feat.is_cuda and dtype != torch.float32:
+            with torch.autocast("cuda", dtype=dtype):
+                return head(feat.float()).float()
+        return head(feat.float())
     l1, l2 = head[0], head[2]
     h = F.relu(F.linear(feat.to(dtype), l1.weight.to(dtype), l1.bias.to(dtype)))
     return F.linear(h, l2.weight.to(dtype), l2.bias.to(dtype)).float()
@@ -117,6 +122,7 @@ class ModelRunner:
         # buffers when something reads them (state_dict: checkpoints, evaluation copies) — no
         # per-step kernel for a counter the training math never reads (momentum is set)
         self._nbt_pending = 0
+        self._nbt_head_pending = 0     # ... of the native BatchNorm projector head (ops/head.py _BNHead)
         # flushed before any state_dict() / load_state_dict() that reaches a BN, called on the
         # top-level model or on any submodule (e.g. model.encoder): the hooks sit on every BN
         # module. A load flushes first, so the loaded counters replace the flushed ones instead
@@ -171,6 +177,10 @@ class ModelRunner:
         if self._nbt_pending and self._nbt:
             torch._foreach_add_(self._nbt, self._nbt_pending)
         self._nbt_pending = 0
+        if self._nbt_head_pending:
+            torch._foreach_add_([m.num_batches_tracked for m in self.model.head.modules()
+                                 if isinstance(m, torch.nn.BatchNorm1d)], self._nbt_head_pending)
+        self._nbt_head_pending = 0
 
     def encode(self, x, training=None):
         enc = self.model.encoder
@@ -187,8 +197,11 @@ class ModelRunner:
     def forward(self, x):
         feat = self.encode(x)
         if self.backend == "native" and self.fused and feat.is_cuda and FUSED_HEAD:
-            from ..ops.head import projection_head
-            return projection_head(feat, self.model.head, self.weight_cache())
+            from ..ops.head import bn_head_native, projection_head
+            head = self.model.head
+            if is_bn_projector(head) and bn_head_native(head, feat):
+                self._nbt_head_pending += 1    # hbn_fwd updates the running statistics, not the counter
+            return projection_head(feat, head, self.weight_cache())
         if self.backend == "native" or (x.is_cuda and self.precision == "bf16"):
             return head_forward(self.model.head, feat)
         return self.model.head(feat)

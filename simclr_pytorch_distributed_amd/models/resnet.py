@@ -3,7 +3,9 @@
 Module tree, parameter names and initialisation follow the reference
 (networks/resnet_big.py:7-204) so that checkpoints cross-load in both directions:
 ``encoder.conv1``, ``encoder.bn1``, ``encoder.layer{1..4}.{i}.{conv,bn}{1,2,3}``,
-``encoder.layer{k}.0.shortcut.{0,1}`` and ``head.{0,2}`` (MLP) / ``head`` (linear).
+``encoder.layer{k}.0.shortcut.{0,1}`` and ``head.{0,2}`` (MLP) / ``head`` (linear). The
+BatchNorm projector ``head='mlp_bn'`` (Barlow Twins / VICReg) is this project's addition:
+``head.{0,3,6}.weight`` and ``head.{1,4}.*`` (BatchNorm1d).
 
 What is different (MI355X-first):
 
@@ -26,7 +28,8 @@ import torch.nn.functional as F
 
 __all__ = [
     "BasicBlock", "Bottleneck", "ResNet", "resnet18", "resnet34", "resnet50", "resnet101",
-    "model_dict", "LinearBatchNorm", "SupConResNet", "SupCEResNet", "LinearClassifier",
+    "model_dict", "LinearBatchNorm", "SupConResNet", "SupCEResNet", "LinearClassifier", "bn_projector",
+    "is_bn_projector",
 ]
 
 
@@ -197,7 +200,8 @@ class SupConResNet(nn.Module):
     """
 
     def __init__(self, name: str = "resnet50", head: str = "mlp", feat_dim: int = 128,
-                 stem: str = "cifar", zero_init_residual: bool = False):
+                 stem: str = "cifar", zero_init_residual: bool = False, head_hidden: int = 0,
+                 head_layers: int = 3):
         super().__init__()
         model_fun, dim_in = model_dict[name]
         self.name = name
@@ -210,11 +214,33 @@ class SupConResNet(nn.Module):
         elif head == "mlp":
             self.head = nn.Sequential(nn.Linear(dim_in, dim_in), nn.ReLU(inplace=True),
                                       nn.Linear(dim_in, feat_dim))
+        elif head == "mlp_bn":
+            self.head = bn_projector(dim_in, head_hidden or dim_in, feat_dim, head_layers)
         else:
             raise NotImplementedError(f"head not supported: {head}")
 
     def forward(self, x):
         return self.head(self.encoder(x))
+
+
+def bn_projector(dim_in: int, hidden: int, feat_dim: int, layers: int = 3) -> nn.Sequential:
+    """The Barlow Twins / VICReg projector: ``layers - 1`` hidden layers Linear(bias=False) ->
+    BatchNorm1d -> ReLU, then Linear(bias=False)."""
+    if layers not in (2, 3):
+        raise ValueError(f"head_layers {layers}: 2 or 3 supported")
+    if hidden % 32 or feat_dim % 32 or hidden < 32 or feat_dim < 32:
+        raise ValueError(f"mlp_bn head: head_hidden {hidden} and feat_dim {feat_dim} must be multiples of 32")
+    mods, d = [], dim_in
+    for _ in range(layers - 1):
+        mods += [nn.Linear(d, hidden, bias=False), nn.BatchNorm1d(hidden), nn.ReLU(inplace=True)]
+        d = hidden
+    return nn.Sequential(*mods, nn.Linear(d, feat_dim, bias=False))
+
+
+def is_bn_projector(head) -> bool:
+    """``head`` has the structure :func:`bn_projector` builds (BatchNorm1d or a converted SyncBatchNorm)."""
+    return isinstance(head, nn.Sequential) and len(head) in (4, 7) and \
+        isinstance(head[1], nn.modules.batchnorm._BatchNorm)
 
 
 class SupCEResNet(nn.Module):

@@ -10,9 +10,19 @@ sinks. The bf16 weights come from the per-step weight cache (ops/weights.py cach
 head's Linear layers as 1x1 convs, in both the forward and the transposed layout).
 Numerics: bf16 operands, fp32 accumulation, fp32 biases, bf16 hidden activation, fp32
 output — the reference computed under autocast, with the bias added before rounding.
+
+The BatchNorm projector (``--head mlp_bn``: Linear -> BatchNorm1d -> ReLU hidden layers, models/resnet.py
+``bn_projector``) is one node as well (``_BNHead``, csrc/bindings/head_bn_ops.cpp): every hidden layer
+is ONE launch per direction of the column-strip-owned kernels of csrc/kernels/head_bn.hip (GEMM +
+batch statistics + normalise + ReLU; BN + ReLU backward with the γ / β gradients), the last Linear
+and the weight / data gradients run on the GEMMs above. Kept for backward per hidden layer: the bf16
+pre-activation and μ, rstd; the activation is recomputed. Outside the kernels' range (2 <= rows <=
+2048, in = 64j <= 8192, hidden = 32j <= 8192), in eval mode and with a SyncBatchNorm head the modules
+run instead (``models/executor.py head_forward``), with one warning.
 """
 from __future__ import annotations
 
+import logging
 import os
 
 import torch
@@ -91,8 +101,74 @@ def _wt(wc, lin) -> torch.Tensor:
     return wc.dgrad(lin).view(lin.in_features, lin.out_features)
 
 
+class _BNHead(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, feat, head, *rest):
+        lins = [m for m in head if isinstance(m, torch.nn.Linear)]
+        bns = [m for m in head if isinstance(m, torch.nn.BatchNorm1d)]
+        L = len(lins)
+        wbs, wts, params = list(rest[:L]), list(rest[L:2 * L]), rest[2 * L:]
+        out = _ext.require().head_bn_fwd(feat, wbs, [b.weight.detach() for b in bns], [b.bias.detach() for b in bns],
+                                         [b.running_mean for b in bns], [b.running_var for b in bns],
+                                         bns[0].momentum, bns[0].eps)
+        ctx.save_for_backward(*out[1:], *wts)       # fb, then (yb, mu, rstd) per hidden layer
+        ctx.mods = (lins, bns)
+        ctx.params = params
+        ctx.feat_dtype = feat.dtype
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, dz):
+        lins, bns = ctx.mods
+        L = len(lins)
+        saved = ctx.saved_tensors
+        fb, per, wts = saved[0], saved[1:1 + 3 * (L - 1)], list(saved[1 + 3 * (L - 1):])
+        t = sinks.target
+        dfeat = _ext.require().head_bn_bwd(dz.float(), fb, list(per[0::3]), list(per[1::3]), list(per[2::3]),
+                                           [b.weight.detach() for b in bns], [b.bias.detach() for b in bns], wts,
+                                           [t(l.weight) for l in lins], [t(b.weight) for b in bns],
+                                           [t(b.bias) for b in bns], _side(dz))
+        sinks.notify(ctx.params)
+        return (dfeat.to(ctx.feat_dtype), None) + (None,) * (2 * L + len(ctx.params))
+
+
+_bn_head_warned = False
+
+
+def bn_head_native(head, feat: torch.Tensor) -> bool:
+    """Can ``head`` (a ``bn_projector``) run on the head_bn kernels for these features? The reason why
+    not is logged once."""
+    global _bn_head_warned
+    bns = [m for m in head if isinstance(m, torch.nn.modules.batchnorm._BatchNorm)]
+    lins = [m for m in head if isinstance(m, torch.nn.Linear)]
+    why = None
+    if not head.training:
+        return False                    # evaluation: the modules, silently (running statistics)
+    if not all(type(b) is torch.nn.BatchNorm1d for b in bns):
+        why = "its BatchNorms are synchronised"
+    elif not all(b.affine and b.track_running_stats and b.momentum == bns[0].momentum and b.eps == bns[0].eps
+                 and b.momentum is not None for b in bns):
+        why = "its BatchNorms differ from affine BatchNorm1d with one momentum and eps"
+    elif not (feat.is_cuda and _ext.require().head_bn_supported(feat.shape[0], lins[0].in_features,
+                                                                lins[0].out_features, len(lins))):
+        why = (f"{feat.shape[0]} rows, {lins[0].in_features} -> {lins[0].out_features} is outside the kernels' range "
+               "(2 <= rows <= 2048, in = 64j <= 8192, hidden = 32j <= 8192)")
+    if why is not None and not _bn_head_warned:
+        _bn_head_warned = True
+        logging.warning(f"mlp_bn head: running as torch modules: {why}")
+    return why is None
+
+
 def projection_head(feat: torch.Tensor, head, wc) -> torch.Tensor:
     """``head(feat)`` in bf16 with fp32 output, as one autograd node."""
+    from ..models.resnet import is_bn_projector
+    if is_bn_projector(head):
+        if not bn_head_native(head, feat):
+            from ..models.executor import head_forward
+            return head_forward(head, feat)
+        lins = [m for m in head if isinstance(m, torch.nn.Linear)]
+        params = [p for m in head for p in m.parameters(recurse=False)]
+        return _BNHead.apply(feat, head, *[_w(wc, l) for l in lins], *[_wt(wc, l) for l in lins], *params)
     if isinstance(head, torch.nn.Linear):
         return _LinearHead.apply(feat, _w(wc, head), _wt(wc, head), head, head.weight, head.bias)
     l1, l2 = head[0], head[2]
