@@ -18,6 +18,7 @@ void register_probe(pybind11::module& m);
 void register_knn(pybind11::module& m);
 void register_barlow(pybind11::module& m);
 void register_vicreg(pybind11::module& m);
+void register_swav(pybind11::module& m);
 
 void register_ops(pybind11::module& m) {
   register_supcon(m);
@@ -36,5 +37,6 @@ void register_ops(pybind11::module& m) {
   register_knn(m);
   register_barlow(m);
   register_vicreg(m);
+  register_swav(m);
 }
 }  // namespace sdx_bind

@@ -140,6 +140,35 @@ hipError_t launch_vic_bwd(const float* z1, const float* z2, const float* G, cons
                           const float* g, int n, int D, double sim_w, double n_total, float* dz1, float* dz2,
                           hipStream_t s);
 
+// ---- SwAV loss (swav.hip, swav_plan.h): bf16x3 MFMA prototype scores, Sinkhorn-Knopp ------
+// z1, z2 [n][D] fp32 (n rows per view on this rank), C [K][D] the prototypes, zhat [2n][D] view-major,
+// rnorm [2n], S / dS [2n][Kp] with Kp = 64·ceil(K / 64) and zero padding columns, r / u [2][K], c [2n].
+// n_total: the batch size N per view of the formulas (= n on one rank). Supported: n >= 2, D = 64·j <=
+// 2048, 2 <= K <= 16384, 2n·Kp < 2^31, 16-byte aligned tensors, eps and temp > 0; everything else is
+// hipErrorInvalidValue before any launch.
+bool swav_supported(long n, long D, long K, long iters);
+// 1 launch: zhat, rnorm; C's rows normalised in place
+hipError_t launch_swav_prep(const float* z1, const float* z2, float* C, int n, int D, int K, float* zhat,
+                            float* rnorm, hipStream_t s);
+// 1 launch: S and part [2][ceil(n / 64)][K], the partials of the first prototype sum Σ_b exp((S − 1)/eps)
+hipError_t launch_swav_scores(const float* zhat, const float* C, int n, int D, int K, double eps, float* S,
+                              float* part, hipStream_t s);
+// 1 launch: part [2][T][K] -> r [2][K]
+hipError_t launch_swav_rowsum(const float* part, int T, int K, float* r, hipStream_t s);
+// 1 launch, one Sinkhorn iteration from r. part != nullptr: [2][ceil(n / 16)][K], the partials of the next
+// r; part == nullptr (the last iteration): u [2][K] and c [2n]
+hipError_t launch_swav_sinkhorn(const float* S, const float* r, int n, int K, double eps, double n_total, float* part,
+                                float* u, float* c, hipStream_t s);
+// 2 launches: dS (not scaled by an upstream gradient), qsum [2n] = Σ_k q, rowloss [n] fp64 workspace,
+// loss = −Σ_b rowloss / (2·n_total), a device scalar
+hipError_t launch_swav_loss_grad(const float* S, const float* u, const float* c, int n, int K, double eps, double temp,
+                                 double n_total, float* dS, float* qsum, double* rowloss, float* loss,
+                                 hipStream_t s);
+// 2 launches: dzhat = dS·C and dz = g·(dzhat − zhat·(zhat·dzhat))·rnorm, both [2n][D]; a third when dC !=
+// nullptr: dC [K][D] = g·dSᵀ·zhat. g: the upstream scalar gradient in device memory
+hipError_t launch_swav_bwd(const float* zhat, const float* rnorm, const float* C, const float* dS, const float* g,
+                           int n, int D, int K, float* dzhat, float* dz, float* dC, hipStream_t s);
+
 // ---- linear-probe sweep: G classifiers on one feature batch (linear_ce_sweep.hip) ----
 // W [G][C][K], bias [G][C], buffers alike, logits / dz [G][B][C], rowstat [G][B][3], stats [G][3].
 // Supported: 1 <= G <= 16, K = 64·2^j <= 2048, 1 <= C <= 1024, B >= 1, G·B·C, B·K and G·C·K

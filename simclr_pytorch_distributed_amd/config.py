@@ -18,6 +18,8 @@ Additions (new flags only; no reference flag changes meaning):
 ``--method BarlowTwins`` with ``--bt_lambda`` (negative-free pretraining objective, losses/barlow.py),
 ``--method VICReg`` with ``--vic_sim`` / ``--vic_std`` / ``--vic_cov`` (variance-invariance-covariance
 objective, losses/vicreg.py),
+``--method SwAV`` with ``--swav_prototypes`` / ``--swav_eps`` / ``--swav_temp`` / ``--swav_iters`` /
+``--swav_freeze_iters`` (two-crop online clustering against trainable prototypes, losses/swav.py),
 ``--head mlp_bn`` with ``--head_hidden`` / ``--head_layers`` (pretraining only: the BatchNorm projector of
 Barlow Twins / VICReg, models/resnet.py ``bn_projector``, natively on csrc/kernels/head_bn.hip),
 ``--val_folder`` / ``--resize`` (ImageFolder evaluation: Resize + CenterCrop on the GPU; the linear
@@ -163,7 +165,7 @@ def pretrain_parser() -> argparse.ArgumentParser:
     p.add_argument("--data_folder", type=str, default=None, help="path to custom dataset")
     p.add_argument("--size", type=int, default=32, help="parameter for RandomResizedCrop")
     # method / temperature (main_supcon.py:59-63)
-    p.add_argument("--method", type=str, default="SimCLR", choices=["SupCon", "SimCLR", "BarlowTwins", "VICReg"])
+    p.add_argument("--method", type=str, default="SimCLR", choices=["SupCon", "SimCLR", "BarlowTwins", "VICReg", "SwAV"])
     p.add_argument("--temp", type=float, default=0.5, help="temperature for loss function")
     # other (main_supcon.py:66-88)
     p.add_argument("--cosine", action="store_true", help="using cosine annealing")
@@ -210,6 +212,9 @@ def pretrain_parser() -> argparse.ArgumentParser:
     for name, what in (("sim", "invariance"), ("std", "variance"), ("cov", "covariance")):
         g.add_argument(f"--vic_{name}", type=float, default=argparse.SUPPRESS, metavar="W",
                        help=f"--method VICReg: weight of the {what} term; default {VIC_WEIGHTS[name]:g}")
+    for name, (kind, what) in SWAV_HELP.items():
+        g.add_argument(f"--swav_{name}", type=kind, default=argparse.SUPPRESS, metavar="V",
+                       help=f"--method SwAV: {what}; default {SWAV_DEFAULTS[name]:g}")
     g.add_argument("--head_hidden", type=int, default=argparse.SUPPRESS, metavar="H",
                    help="--head mlp_bn: width of the hidden layers, a multiple of 32; default: the encoder's "
                         "output width (2048 for resnet50)")
@@ -222,6 +227,12 @@ def pretrain_parser() -> argparse.ArgumentParser:
 
 BT_LAMBDA = 0.0051
 VIC_WEIGHTS = {"sim": 25.0, "std": 25.0, "cov": 1.0}
+SWAV_DEFAULTS = {"prototypes": 3000, "eps": 0.05, "temp": 0.1, "iters": 3, "freeze_iters": 313}
+SWAV_HELP = {"prototypes": (int, "number of prototypes K, 2 to 16384 on the native kernels"),
+             "eps": (float, "entropy regularisation of the Sinkhorn-Knopp codes"),
+             "temp": (float, "temperature of the prototype softmax"),
+             "iters": (int, "Sinkhorn-Knopp iterations"),
+             "freeze_iters": (int, "training iterations during which the prototypes get a zero gradient")}
 
 
 def _finish_common(opt, prefix_dirs: bool):
@@ -280,6 +291,22 @@ def parse_pretrain(argv: Optional[Sequence[str]] = None, make_dirs: bool = True,
                 raise ValueError(f"--vic_{name} must be finite and >= 0")
         elif hasattr(opt, "vic_" + name):
             raise ValueError(f"--vic_{name} needs --method VICReg")
+    if opt.method == "SwAV":
+        sw = {k: getattr(opt, "swav_" + k, v) for k, v in SWAV_DEFAULTS.items()}
+        if sw["prototypes"] < 2 or not 0.0 < sw["eps"] < math.inf or not 0.0 < sw["temp"] < math.inf \
+                or sw["iters"] < 1 or sw["freeze_iters"] < 0:
+            raise ValueError("--swav_prototypes >= 2, --swav_eps > 0, --swav_temp > 0, --swav_iters >= 1 and "
+                             "--swav_freeze_iters >= 0 are required")
+        if getattr(opt, "cuda_graph", False) and sw["freeze_iters"] > 0:
+            raise ValueError("--method SwAV with --cuda_graph needs --swav_freeze_iters 0: a captured step cannot "
+                             "switch the prototypes' gradient on")
+        if opt.micro_batch > 0:
+            raise ValueError("--method SwAV cannot run with --micro_batch: the Sinkhorn codes couple the rows of "
+                             "the whole batch, and the prototypes take their gradient in the loss pass")
+    else:
+        for name in SWAV_DEFAULTS:
+            if hasattr(opt, "swav_" + name):
+                raise ValueError(f"--swav_{name} needs --method SwAV")
     if opt.head == "mlp_bn":
         if opt.micro_batch > 0:
             raise ValueError("--head mlp_bn cannot run with --micro_batch: gradient caching takes the head's rows "

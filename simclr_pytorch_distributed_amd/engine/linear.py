@@ -73,7 +73,8 @@ class LinearEngine:
             model = SupConResNet(opt.model, opt.head, opt.feat_dim, opt.stem)
             if opt.ckpt:
                 st = ckpt_mod.load_checkpoint(opt.ckpt)
-                sd = ckpt_mod.strip_prefix(st["model"])
+                # (a --method SwAV run's prototype layer is not part of the probe's model)
+                sd = {k: v for k, v in ckpt_mod.strip_prefix(st["model"]).items() if not k.startswith("prototypes.")}
                 own = model.state_dict()
                 if {k for k in sd if k.startswith("head")} != {k for k in own if k.startswith("head")}:
                     # another projector than --head builds here (a --head mlp_bn pretraining run):

@@ -47,12 +47,17 @@ class PretrainEngine(TrainEngine):
     def _build_model(self):
         opt = self.opt
         model = SupConResNet(opt.model, opt.head, opt.feat_dim, opt.stem, head_hidden=getattr(opt, "head_hidden", 0),
-                             head_layers=getattr(opt, "head_layers", 3))
+                             head_layers=getattr(opt, "head_layers", 3), n_prototypes=self._swav("prototypes"))
         if opt.ckpt:
             sd = ckpt_mod.load_checkpoint(opt.ckpt)["model"]
             ckpt_mod.load_model_state(model, sd)
             logging.info(f"load model from {opt.ckpt} ...")
         return model
+
+    def _swav(self, name: str):
+        """--swav_<name> or its default; 0 for every other method."""
+        from ..config import SWAV_DEFAULTS
+        return getattr(self.opt, "swav_" + name, SWAV_DEFAULTS[name]) if self.opt.method == "SwAV" else 0
 
     def _setup_more_comm(self, opt, dev):
         if self.world > 1 and self.backend == "native":
@@ -110,6 +115,15 @@ class PretrainEngine(TrainEngine):
             self.criterion = VICRegLoss(*(getattr(opt, "vic_" + k, v) for k, v in VIC_WEIGHTS.items()),
                                         backend=loss_backend)
             logging.info("VICReg: --temp, --base_temperature and --contrast_mode are ignored")
+        elif opt.method == "SwAV":
+            from ..losses.swav import SwAVLoss
+            # The prototypes are a parameter of the model: flat buffer, optimizer, reducer, checkpoint.
+            # While they are frozen their gradient is zero, but weight decay still shrinks every row
+            # radially; the criterion's normalisation before each forward undoes exactly that, so the
+            # rows keep their direction until the freeze ends.
+            self.criterion = SwAVLoss(self.model.prototypes.weight, self._swav("eps"), self._swav("temp"),
+                                      self._swav("iters"), backend=loss_backend)
+            logging.info("SwAV: --temp, --base_temperature and --contrast_mode are ignored")
         else:
             self.criterion = DistributedContrastiveLoss(opt.method, opt.temp, opt.base_temperature,
                                                         opt.contrast_mode, backend=loss_backend)
@@ -180,6 +194,10 @@ class PretrainEngine(TrainEngine):
     def _host_prelude(self, epoch: int, it: int, iters: int):
         super()._host_prelude(epoch, it, iters)
         opt = self.opt
+        if opt.method == "SwAV":
+            # the iteration count lives on the host: no device sync (config.py refuses --cuda_graph with a
+            # freeze, since a captured step keeps the kernels it was captured with)
+            self.criterion.set_frozen(self.global_step < self._swav("freeze_iters"))
         if opt.sec or opt.l2reg:
             now_iter = (epoch - 1) * iters + it
             self._ramp_t.fill_(now_iter / (opt.epochs * iters))

@@ -1,2 +1,3 @@
 from .barlow import BarlowTwinsLoss, barlow_reference  # noqa: F401
 from .vicreg import VICRegLoss, vicreg_reference  # noqa: F401
+from .swav import SwAVLoss, swav_reference  # noqa: F401

@@ -201,7 +201,7 @@ class SupConResNet(nn.Module):
 
     def __init__(self, name: str = "resnet50", head: str = "mlp", feat_dim: int = 128,
                  stem: str = "cifar", zero_init_residual: bool = False, head_hidden: int = 0,
-                 head_layers: int = 3):
+                 head_layers: int = 3, n_prototypes: int = 0):
         super().__init__()
         model_fun, dim_in = model_dict[name]
         self.name = name
@@ -218,6 +218,9 @@ class SupConResNet(nn.Module):
             self.head = bn_projector(dim_in, head_hidden or dim_in, feat_dim, head_layers)
         else:
             raise NotImplementedError(f"head not supported: {head}")
+        if n_prototypes > 0:
+            # SwAV's prototype layer: read by the criterion (losses/swav.py), not by forward
+            self.prototypes = nn.Linear(feat_dim, n_prototypes, bias=False)
 
     def forward(self, x):
         return self.head(self.encoder(x))
