@@ -19,6 +19,7 @@ void register_knn(pybind11::module& m);
 void register_barlow(pybind11::module& m);
 void register_vicreg(pybind11::module& m);
 void register_swav(pybind11::module& m);
+void register_moco(pybind11::module& m);
 
 void register_ops(pybind11::module& m) {
   register_supcon(m);
@@ -38,5 +39,6 @@ void register_ops(pybind11::module& m) {
   register_barlow(m);
   register_vicreg(m);
   register_swav(m);
+  register_moco(m);
 }
 }  // namespace sdx_bind

@@ -169,6 +169,26 @@ hipError_t launch_swav_loss_grad(const float* S, const float* u, const float* c,
 hipError_t launch_swav_bwd(const float* zhat, const float* rnorm, const float* C, const float* dS, const float* g,
                            int n, int D, int K, float* dzhat, float* dz, float* dC, hipStream_t s);
 
+// ---- MoCo loss (moco.hip, moco_plan.h): queue-streaming bf16x3 MFMA InfoNCE --------------------
+// q, k, qhat, khat, dq [n][D] fp32 (n rows on this rank), rq, lpos, lse [n], queue [2][K][D] bf16 (hi and
+// lo plane, value hi + lo), part [splits][n][2], slab [splits][n][D] (sizes: moco_plan.h), ptr a device
+// int64. n_total: the global batch (>= n). Supported: n >= 1, D = 64·j <= 256, K = 64·j in [64, 2^20],
+// index products below 2^31, 16-byte aligned tensors, temp > 0; everything else is hipErrorInvalidValue
+// before any launch.
+bool moco_supported(long n, long D, long K);
+// 1 launch: qhat, rq = 1/‖q‖, khat, lpos = qhat·khat per row
+hipError_t launch_moco_prep(const float* q, const float* k, int n, int D, float* qhat, float* rq, float* khat,
+                            float* lpos, hipStream_t s);
+// 2 launches: part, then lse and loss = −Σ_i (lpos_i/T − lse_i) / n_total, a device scalar
+hipError_t launch_moco_fwd(const float* qhat, const float* lpos, const uint16_t* queue, int n, int D, int K,
+                           double temp, double n_total, float* part, float* lse, float* loss, hipStream_t s);
+// 2 launches: slab, then dq (scaled by the upstream scalar gradient g in device memory)
+hipError_t launch_moco_bwd(const float* qhat, const float* rq, const float* khat, const uint16_t* queue,
+                           const float* lse, const float* lpos, const float* g, int n, int D, int K, double temp,
+                           double n_total, float* slab, float* dq, hipStream_t s);
+// 2 launches: keys [n][D] (n <= K, 8-byte aligned) into slots (ptr + i) mod K, then ptr = (ptr + n) mod K
+hipError_t launch_moco_enqueue(const float* keys, int n, int D, int K, int64_t* ptr, uint16_t* queue, hipStream_t s);
+
 // ---- linear-probe sweep: G classifiers on one feature batch (linear_ce_sweep.hip) ----
 // W [G][C][K], bias [G][C], buffers alike, logits / dz [G][B][C], rowstat [G][B][3], stats [G][3].
 // Supported: 1 <= G <= 16, K = 64·2^j <= 2048, 1 <= C <= 1024, B >= 1, G·B·C, B·K and G·C·K
@@ -441,6 +461,8 @@ hipError_t launch_sgd(float* p, const float* g, float* buf, long n, const float*
 hipError_t launch_lars(float* p, const float* g, float* buf, const long* seg_off, const int* adapt, int nseg, long n,
                        const float* lr, float momentum, float wd, float gscale, float eta, float* norms,
                        float* part, hipStream_t s);
+// 1 launch: dst = m·dst + (1 − m)·src over n floats (both 16-byte aligned, 0 <= m <= 1), rounded once
+hipError_t launch_ema_update(float* dst, const float* src, long n, double m, hipStream_t s);
 
 // ---- pooling (pool.hip) ---------------------------------------------------------
 hipError_t launch_maxpool_fwd(const void* x, void* y, int N, int H, int W, int C, int P, int Q, int k, int stride,

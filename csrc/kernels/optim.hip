@@ -134,7 +134,42 @@ __global__ __launch_bounds__(256) void lars_kernel(float* __restrict__ p, const 
   }
 }
 
+// momentum encoder (MoCo): dst = m·dst + (1 − m)·src. m is a double passed by value and both products
+// are fp64, so an element is rounded once; float4 over the 16-byte aligned body, the n % 4 tail by
+// the first threads.
+__global__ __launch_bounds__(256) void ema_kernel(float* __restrict__ dst, const float* __restrict__ src, long n,
+                                                  double m) {
+  const double om = 1.0 - m;
+  const long n4 = n / 4;
+  const long t0 = blockIdx.x * (long)blockDim.x + threadIdx.x, stride = (long)gridDim.x * blockDim.x;
+  float4* D4 = reinterpret_cast<float4*>(dst);
+  const float4* S4 = reinterpret_cast<const float4*>(src);
+  for (long i = t0; i < n4; i += stride) {
+    float4 d = D4[i];
+    const float4 v = S4[i];
+    d.x = (float)(m * (double)d.x + om * (double)v.x);
+    d.y = (float)(m * (double)d.y + om * (double)v.y);
+    d.z = (float)(m * (double)d.z + om * (double)v.z);
+    d.w = (float)(m * (double)d.w + om * (double)v.w);
+    D4[i] = d;
+  }
+  const long e = 4 * n4 + t0;
+  if (e < n) dst[e] = (float)(m * (double)dst[e] + om * (double)src[e]);
+}
+
 }  // namespace
+
+hipError_t launch_ema_update(float* dst, const float* src, long n, double m, hipStream_t s) {
+  if (dst == nullptr || src == nullptr || n < 1 || !(m >= 0.0 && m <= 1.0) || ((uintptr_t)dst & 15) != 0 ||
+      ((uintptr_t)src & 15) != 0)
+    return hipErrorInvalidValue;
+  long grid = (n / 4 + 255) / 256;
+  if (grid > 4096) grid = 4096;
+  if (grid < 1) grid = 1;
+  hipLaunchKernelGGL(ema_kernel, dim3(grid), dim3(256), 0, s, dst, src, n, m);
+  SDX_LAUNCH_CHECK();
+  return hipSuccess;
+}
 
 hipError_t launch_sgd(float* p, const float* g, float* buf, long n, const float* lr, float momentum, float wd,
                       float gscale, int nesterov, hipStream_t s, int max_blocks) {

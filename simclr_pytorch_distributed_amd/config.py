@@ -20,6 +20,8 @@ Additions (new flags only; no reference flag changes meaning):
 objective, losses/vicreg.py),
 ``--method SwAV`` with ``--swav_prototypes`` / ``--swav_eps`` / ``--swav_temp`` / ``--swav_iters`` /
 ``--swav_freeze_iters`` (two-crop online clustering against trainable prototypes, losses/swav.py),
+``--method MoCo`` with ``--moco_k`` / ``--moco_m`` / ``--moco_temp`` (MoCo v2: momentum key encoder and a
+queue of negatives, losses/moco.py),
 ``--head mlp_bn`` with ``--head_hidden`` / ``--head_layers`` (pretraining only: the BatchNorm projector of
 Barlow Twins / VICReg, models/resnet.py ``bn_projector``, natively on csrc/kernels/head_bn.hip),
 ``--val_folder`` / ``--resize`` (ImageFolder evaluation: Resize + CenterCrop on the GPU; the linear
@@ -165,7 +167,7 @@ def pretrain_parser() -> argparse.ArgumentParser:
     p.add_argument("--data_folder", type=str, default=None, help="path to custom dataset")
     p.add_argument("--size", type=int, default=32, help="parameter for RandomResizedCrop")
     # method / temperature (main_supcon.py:59-63)
-    p.add_argument("--method", type=str, default="SimCLR", choices=["SupCon", "SimCLR", "BarlowTwins", "VICReg", "SwAV"])
+    p.add_argument("--method", type=str, default="SimCLR", choices=["SupCon", "SimCLR", "BarlowTwins", "VICReg", "SwAV", "MoCo"])
     p.add_argument("--temp", type=float, default=0.5, help="temperature for loss function")
     # other (main_supcon.py:66-88)
     p.add_argument("--cosine", action="store_true", help="using cosine annealing")
@@ -215,6 +217,9 @@ def pretrain_parser() -> argparse.ArgumentParser:
     for name, (kind, what) in SWAV_HELP.items():
         g.add_argument(f"--swav_{name}", type=kind, default=argparse.SUPPRESS, metavar="V",
                        help=f"--method SwAV: {what}; default {SWAV_DEFAULTS[name]:g}")
+    for name, (kind, what) in MOCO_HELP.items():
+        g.add_argument(f"--moco_{name}", type=kind, default=argparse.SUPPRESS, metavar="V",
+                       help=f"--method MoCo: {what}; default {MOCO_DEFAULTS[name]:g}")
     g.add_argument("--head_hidden", type=int, default=argparse.SUPPRESS, metavar="H",
                    help="--head mlp_bn: width of the hidden layers, a multiple of 32; default: the encoder's "
                         "output width (2048 for resnet50)")
@@ -233,6 +238,10 @@ SWAV_HELP = {"prototypes": (int, "number of prototypes K, 2 to 16384 on the nati
              "temp": (float, "temperature of the prototype softmax"),
              "iters": (int, "Sinkhorn-Knopp iterations"),
              "freeze_iters": (int, "training iterations during which the prototypes get a zero gradient")}
+MOCO_DEFAULTS = {"k": 65536, "m": 0.999, "temp": 0.2}
+MOCO_HELP = {"k": (int, "queue length K, a multiple of 64 in [64, 2^20] on the native kernels"),
+             "m": (float, "momentum of the key encoder's EMA"),
+             "temp": (float, "temperature of the InfoNCE logits")}
 
 
 def _finish_common(opt, prefix_dirs: bool):
@@ -307,6 +316,20 @@ def parse_pretrain(argv: Optional[Sequence[str]] = None, make_dirs: bool = True,
         for name in SWAV_DEFAULTS:
             if hasattr(opt, "swav_" + name):
                 raise ValueError(f"--swav_{name} needs --method SwAV")
+    if opt.method == "MoCo":
+        mo = {k: getattr(opt, "moco_" + k, v) for k, v in MOCO_DEFAULTS.items()}
+        if mo["k"] < opt.batch_size or not 0.0 <= mo["m"] <= 1.0 or not 0.0 < mo["temp"] < math.inf:
+            raise ValueError("--moco_k >= --batch_size, 0 <= --moco_m <= 1 and --moco_temp > 0 are required")
+        if opt.micro_batch > 0:
+            raise ValueError("--method MoCo cannot run with --micro_batch: the key encoder sees the whole batch "
+                             "once per step, and its BatchNorm statistics would change with the chunks")
+        if getattr(opt, "cuda_graph", False):
+            raise ValueError("--method MoCo cannot run with --cuda_graph: the step has no host sync and the queue "
+                             "pointer lives on the device, but a captured step has not been validated")
+    else:
+        for name in MOCO_DEFAULTS:
+            if hasattr(opt, "moco_" + name):
+                raise ValueError(f"--moco_{name} needs --method MoCo")
     if opt.head == "mlp_bn":
         if opt.micro_batch > 0:
             raise ValueError("--head mlp_bn cannot run with --micro_batch: gradient caching takes the head's rows "

@@ -319,10 +319,14 @@ class TrainEngine:
         extra = st.get("sdx_state") or {}
         self.global_step = int(extra.get("global_step", 0))
         self._resume_extra(extra)
+        self._resume_more(st)
         logging.info(f"resumed from {path} at epoch {self.start_epoch}")
 
     def _resume_extra(self, extra: dict):
         """Take the subclass's own keys of a checkpoint's ``sdx_state``."""
+
+    def _resume_more(self, st: dict):
+        """Take the subclass's own top-level entries of the loaded checkpoint."""
 
     def _extra_state(self, epoch):
         return {"global_step": self.global_step, "epoch": epoch}

@@ -48,7 +48,9 @@ def model_state_with_prefix(model: torch.nn.Module, prefix: str = PREFIX) -> Dic
     return out
 
 
-def save_model(model, optimizer, opt, epoch: int, save_file: str, extra: Optional[Dict] = None):
+def save_model(model, optimizer, opt, epoch: int, save_file: str, extra: Optional[Dict] = None,
+               more: Optional[Dict] = None):
+    """``more``: further top-level entries (MoCo: ``model_k``, ``moco_queue``, ``moco_ptr``)."""
     print("==> Saving...")
     state = {
         "opt": opt_to_dict(opt),
@@ -58,6 +60,8 @@ def save_model(model, optimizer, opt, epoch: int, save_file: str, extra: Optiona
     }
     if extra:
         state["sdx_state"] = extra
+    if more:
+        state.update(more)
     tmp = save_file + ".tmp"
     torch.save(state, tmp)
     os.replace(tmp, save_file)

@@ -124,6 +124,8 @@ class PretrainEngine(TrainEngine):
             self.criterion = SwAVLoss(self.model.prototypes.weight, self._swav("eps"), self._swav("temp"),
                                       self._swav("iters"), backend=loss_backend)
             logging.info("SwAV: --temp, --base_temperature and --contrast_mode are ignored")
+        elif opt.method == "MoCo":
+            self._init_moco(loss_backend)
         else:
             self.criterion = DistributedContrastiveLoss(opt.method, opt.temp, opt.base_temperature,
                                                         opt.contrast_mode, backend=loss_backend)
@@ -136,6 +138,92 @@ class PretrainEngine(TrainEngine):
         self._graph_stats = None
         self._graph_failed = False
         self.knn = self._build_knn(self.train) if getattr(opt, "knn_freq", 0) > 0 else None
+
+    def _moco(self, name: str):
+        """--moco_<name> or its default."""
+        from ..config import MOCO_DEFAULTS
+        return getattr(self.opt, "moco_" + name, MOCO_DEFAULTS[name])
+
+    def _init_moco(self, loss_backend: str):
+        """The momentum (key) encoder and the queue. The key encoder is a copy of the model as it
+        stands (after --ckpt), re-homed into a flat buffer of its own with the layout of the query
+        encoder's, so the EMA is one kernel over the two buffers. It has no gradients and is outside
+        the optimizer and the reducer; its BN buffers are its own (updated by its train-mode forward)."""
+        import copy
+        from ..losses.moco import MoCoLoss
+        from ..models.executor import ModelRunner
+        from ..optim.flat import FlatParams
+        opt = self.opt
+        self.model_k = copy.deepcopy(self.model)
+        self.flat_k = FlatParams(self.model_k)
+        assert self.flat_k.total == self.flat.total and self.flat_k.offsets == self.flat.offsets
+        self.flat_k.grad = None
+        for p in self.model_k.parameters():
+            p.grad = None
+            p.requires_grad_(False)
+        self.runner_k = ModelRunner(self.model_k, self.backend, opt.precision, self.sync_group, master=self.flat_k.flat)
+        self.criterion = MoCoLoss(self._moco("k"), opt.feat_dim, self._moco("temp"), backend=loss_backend,
+                                  seed=opt.seed).to(self.device)
+        self._ema_native = self.backend == "native"
+        logging.info("MoCo: --temp, --base_temperature and --contrast_mode are ignored")
+        if self.world > 1 and not opt.syncBN:
+            logging.info("MoCo: BatchNorm statistics are per rank and unshuffled (no shuffle-BN); use --syncBN")
+
+    def _step_body_moco(self, idx: torch.Tensor, epoch: int, it: int):
+        """θ_k <- m·θ_k + (1 − m)·θ_q, q = f_q(view 1), k = f_k(view 2) without gradient, the loss, the
+        update of θ_q, then the keys enter the queue. No host syncs."""
+        ph = self.prof.phase
+        with ph("augment"):
+            zeroed, x = self._start_step(idx, epoch, it)
+        with ph("forward"):
+            m = self._moco("m")
+            if self._ema_native:
+                from ..ops import moco as moco_ops
+                moco_ops.ema_update(self.flat_k.flat, self.flat.flat, m)
+            else:
+                with torch.no_grad():
+                    self.flat_k.flat.mul_(m).add_(self.flat.flat, alpha=1.0 - m)
+            b = x.shape[0] // 2
+            q = self.runner.forward(x[:b])
+            with torch.no_grad():
+                k = self.runner_k.forward(x[b:]).float()
+        with ph("loss"):
+            loss = self.criterion(q.float(), k)
+            stats = self._norm_terms(q)
+            extra = stats.pop("extra_loss")
+            if extra is not None:
+                loss = loss + extra
+        self._backward_and_update(loss, zeroed)
+        self.criterion.enqueue(k)
+        stats["loss_local"] = loss.detach()
+        return stats
+
+    def _save(self, epoch: int, name: str):
+        if self.opt.method != "MoCo":
+            return super()._save(epoch, name)
+        f = os.path.join(self.opt.save_folder, name)
+        self.runner_k.flush_bn_counters()
+        extra = dict(self._extra_state(epoch))
+        ckpt_mod.save_model(self.model, self.optimizer, self.opt, epoch, f, extra,
+                            more={"model_k": ckpt_mod.model_state_with_prefix(self.model_k),
+                                  "moco_queue": self.criterion.queue.detach().cpu().clone(),
+                                  "moco_ptr": self.criterion.ptr.detach().cpu().clone()})
+
+    def _resume_more(self, st):
+        if self.opt.method == "MoCo":
+            ckpt_mod.load_model_state(self.model_k, st["model_k"])
+            with torch.no_grad():
+                self.criterion.queue.copy_(st["moco_queue"])
+                self.criterion.ptr.copy_(st["moco_ptr"])
+
+    @contextlib.contextmanager
+    def _training_state_kept(self):
+        # the key runner's host-side BN pass counter, next to what the base keeps
+        pend_k = self.runner_k._nbt_pending if self.opt.method == "MoCo" else None
+        with super()._training_state_kept():
+            yield
+        if pend_k is not None:
+            self.runner_k._nbt_pending = pend_k
 
     def _build_knn(self, train: DeviceStore):
         """The weighted k-NN monitor (--knn_freq): bank = the training images already resident
@@ -188,7 +276,10 @@ class PretrainEngine(TrainEngine):
         return dict(super()._extra_state(epoch), record_norm_mean=float(self.record_norm_mean) if valid else None)
 
     def _state_tensors(self):
-        return super()._state_tensors() + [self.record_norm_mean, self._rnm_valid]
+        more = []
+        if self.opt.method == "MoCo":
+            more = [self.flat_k.flat, *self.model_k.buffers(), self.criterion.queue, self.criterion.ptr]
+        return super()._state_tensors() + [self.record_norm_mean, self._rnm_valid] + more
 
     # ------------------------------------------------------------------------------
     def _host_prelude(self, epoch: int, it: int, iters: int):
@@ -206,6 +297,8 @@ class PretrainEngine(TrainEngine):
         """Device work of one step: no host syncs, no host-dependent control flow
         (capturable into a hipGraph)."""
         opt = self.opt
+        if opt.method == "MoCo":
+            return self._step_body_moco(idx, epoch, it)
         mb = getattr(opt, "micro_batch", 0) or 0
         if 0 < mb < 2 * idx.numel():
             return self._step_body_gradcache(idx, epoch, it, mb)
