@@ -20,6 +20,7 @@ void register_barlow(pybind11::module& m);
 void register_vicreg(pybind11::module& m);
 void register_swav(pybind11::module& m);
 void register_moco(pybind11::module& m);
+void register_dino(pybind11::module& m);
 
 void register_ops(pybind11::module& m) {
   register_supcon(m);
@@ -40,5 +41,6 @@ void register_ops(pybind11::module& m) {
   register_vicreg(m);
   register_swav(m);
   register_moco(m);
+  register_dino(m);
 }
 }  // namespace sdx_bind

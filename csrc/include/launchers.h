@@ -189,6 +189,33 @@ hipError_t launch_moco_bwd(const float* qhat, const float* rq, const float* khat
 // 2 launches: keys [n][D] (n <= K, 8-byte aligned) into slots (ptr + i) mod K, then ptr = (ptr + n) mod K
 hipError_t launch_moco_enqueue(const float* keys, int n, int D, int K, int64_t* ptr, uint16_t* queue, hipStream_t s);
 
+// ---- DINO loss (dino.hip, dino_plan.h): both logit matrices streamed through bf16x3 MFMA tiles ----
+// zs, zt, dz [2n][D] fp32 (the two views of the n samples of this rank stacked; teacher row (v, i) goes
+// with student row (1 − v, i)), vs, vt, dv [K][D] (unnormalised prototype weights), the planes bf16
+// [2][rp][D] / [2][K][D] (hi and lo, rp = 2·64·ceil(n / 64), pad rows zero), rzs [2n], rvs [K], rzt64 [2n],
+// zsum [D] fp64, center [K], lse_s / lse_t [rp], part, zslab, vslab as dino_plan.h sizes them. n_total: the
+// global batch per view (>= n). Supported: n >= 1, D = 64·j <= 256, K = 64·j in [64, 131072], 16-byte
+// aligned tensors, temperatures > 0; everything else is hipErrorInvalidValue before any launch.
+bool dino_supported(long n, long D, long K);
+// 2 launches: the four operands normalised and split into planes, 1/‖·‖ of the student's, then zsum = Σ ẑ_t
+hipError_t launch_dino_prep(const float* zs, const float* zt, const float* vs, const float* vt, int n, int D, int K,
+                            uint16_t* zs_pl, uint16_t* zt_pl, uint16_t* cs_pl, uint16_t* ct_pl, float* rzs, float* rvs,
+                            double* rzt64, double* zsum, hipStream_t s);
+// 2 launches: part, then lse_s, lse_t and loss = Σ_rows (lse_s − Σ_k p_t·s/τ_s) / (2·n_total), a device scalar
+hipError_t launch_dino_fwd(const uint16_t* zs_pl, const uint16_t* zt_pl, const uint16_t* cs_pl, const uint16_t* ct_pl,
+                           const float* center, int n, int D, int K, double temp_s, double temp_t, double n_total,
+                           float* part, float* lse_s, float* lse_t, float* loss, hipStream_t s);
+// 2 launches for dz; with dv != nullptr 1 more (the epilogue writes dV) or 2 (vslab, then dV). g: the
+// upstream scalar gradient in device memory
+hipError_t launch_dino_bwd(const float* zs, const float* vs, const uint16_t* zs_pl, const uint16_t* zt_pl,
+                           const uint16_t* cs_pl, const uint16_t* ct_pl, const float* rzs, const float* rvs,
+                           const float* center, const float* lse_s, const float* lse_t, const float* g, int n, int D,
+                           int K, double temp_s, double temp_t, double n_total, float* zslab, float* vslab, float* dz,
+                           float* dv, hipStream_t s);
+// 1 launch: out = m·center + (1 − m)·(vt_k / ‖vt_k‖)·zsum / rows_total, rows_total = 2·n_total
+hipError_t launch_dino_center(const float* vt, const double* zsum, const float* center, int K, int D, double m,
+                              double rows_total, float* out, hipStream_t s);
+
 // ---- linear-probe sweep: G classifiers on one feature batch (linear_ce_sweep.hip) ----
 // W [G][C][K], bias [G][C], buffers alike, logits / dz [G][B][C], rowstat [G][B][3], stats [G][3].
 // Supported: 1 <= G <= 16, K = 64·2^j <= 2048, 1 <= C <= 1024, B >= 1, G·B·C, B·K and G·C·K

@@ -22,6 +22,9 @@ objective, losses/vicreg.py),
 ``--swav_freeze_iters`` (two-crop online clustering against trainable prototypes, losses/swav.py),
 ``--method MoCo`` with ``--moco_k`` / ``--moco_m`` / ``--moco_temp`` (MoCo v2: momentum key encoder and a
 queue of negatives, losses/moco.py),
+``--method DINO`` with ``--dino_prototypes`` / ``--dino_student_temp`` / ``--dino_teacher_temp`` /
+``--dino_warmup_teacher_temp`` / ``--dino_warmup_epochs`` / ``--dino_m`` / ``--dino_center_m`` /
+``--dino_freeze_iters`` (two-crop self-distillation from a momentum teacher, losses/dino.py),
 ``--head mlp_bn`` with ``--head_hidden`` / ``--head_layers`` (pretraining only: the BatchNorm projector of
 Barlow Twins / VICReg, models/resnet.py ``bn_projector``, natively on csrc/kernels/head_bn.hip),
 ``--val_folder`` / ``--resize`` (ImageFolder evaluation: Resize + CenterCrop on the GPU; the linear
@@ -167,7 +170,7 @@ def pretrain_parser() -> argparse.ArgumentParser:
     p.add_argument("--data_folder", type=str, default=None, help="path to custom dataset")
     p.add_argument("--size", type=int, default=32, help="parameter for RandomResizedCrop")
     # method / temperature (main_supcon.py:59-63)
-    p.add_argument("--method", type=str, default="SimCLR", choices=["SupCon", "SimCLR", "BarlowTwins", "VICReg", "SwAV", "MoCo"])
+    p.add_argument("--method", type=str, default="SimCLR", choices=["SupCon", "SimCLR", "BarlowTwins", "VICReg", "SwAV", "MoCo", "DINO"])
     p.add_argument("--temp", type=float, default=0.5, help="temperature for loss function")
     # other (main_supcon.py:66-88)
     p.add_argument("--cosine", action="store_true", help="using cosine annealing")
@@ -220,6 +223,9 @@ def pretrain_parser() -> argparse.ArgumentParser:
     for name, (kind, what) in MOCO_HELP.items():
         g.add_argument(f"--moco_{name}", type=kind, default=argparse.SUPPRESS, metavar="V",
                        help=f"--method MoCo: {what}; default {MOCO_DEFAULTS[name]:g}")
+    for name, (kind, what) in DINO_HELP.items():
+        g.add_argument(f"--dino_{name}", type=kind, default=argparse.SUPPRESS, metavar="V",
+                       help=f"--method DINO: {what}; default {DINO_DEFAULTS[name]}")
     g.add_argument("--head_hidden", type=int, default=argparse.SUPPRESS, metavar="H",
                    help="--head mlp_bn: width of the hidden layers, a multiple of 32; default: the encoder's "
                         "output width (2048 for resnet50)")
@@ -242,6 +248,17 @@ MOCO_DEFAULTS = {"k": 65536, "m": 0.999, "temp": 0.2}
 MOCO_HELP = {"k": (int, "queue length K, a multiple of 64 in [64, 2^20] on the native kernels"),
              "m": (float, "momentum of the key encoder's EMA"),
              "temp": (float, "temperature of the InfoNCE logits")}
+# freeze_iters None: one epoch's iterations (the engine knows the dataset)
+DINO_DEFAULTS = {"prototypes": 65536, "student_temp": 0.1, "teacher_temp": 0.04, "warmup_teacher_temp": 0.04,
+                 "warmup_epochs": 0, "m": 0.996, "center_m": 0.9, "freeze_iters": None}
+DINO_HELP = {"prototypes": (int, "number of prototypes K, a multiple of 64 in [64, 131072] on the native kernels"),
+             "student_temp": (float, "temperature of the student's softmax"),
+             "teacher_temp": (float, "temperature of the teacher's softmax after the warm-up"),
+             "warmup_teacher_temp": (float, "teacher temperature at the start, raised linearly over the warm-up"),
+             "warmup_epochs": (int, "epochs of the teacher temperature's warm-up"),
+             "m": (float, "base momentum of the teacher's EMA, raised to 1 over the run on a cosine"),
+             "center_m": (float, "momentum of the centre of the teacher logits"),
+             "freeze_iters": (int, "training iterations during which the prototypes get a zero gradient (one epoch's)")}
 
 
 def _finish_common(opt, prefix_dirs: bool):
@@ -330,6 +347,24 @@ def parse_pretrain(argv: Optional[Sequence[str]] = None, make_dirs: bool = True,
         for name in MOCO_DEFAULTS:
             if hasattr(opt, "moco_" + name):
                 raise ValueError(f"--moco_{name} needs --method MoCo")
+    if opt.method == "DINO":
+        dn = {k: getattr(opt, "dino_" + k, v) for k, v in DINO_DEFAULTS.items()}
+        if dn["prototypes"] < 2 or not all(0.0 < dn[k] < math.inf for k in ("student_temp", "teacher_temp",
+                                                                             "warmup_teacher_temp")) \
+                or dn["warmup_epochs"] < 0 or not 0.0 <= dn["m"] <= 1.0 or not 0.0 <= dn["center_m"] <= 1.0 \
+                or (dn["freeze_iters"] is not None and dn["freeze_iters"] < 0):
+            raise ValueError("--dino_prototypes >= 2, the --dino_*_temp > 0, --dino_warmup_epochs >= 0, --dino_m and "
+                             "--dino_center_m in [0, 1] and --dino_freeze_iters >= 0 are required")
+        if opt.micro_batch > 0:
+            raise ValueError("--method DINO cannot run with --micro_batch: the teacher sees the whole batch once per "
+                             "step, and the prototypes take their gradient in the loss pass")
+        if getattr(opt, "cuda_graph", False):
+            raise ValueError("--method DINO cannot run with --cuda_graph: the momentum, the teacher temperature and "
+                             "the prototypes' freeze change from the host every step")
+    else:
+        for name in DINO_DEFAULTS:
+            if hasattr(opt, "dino_" + name):
+                raise ValueError(f"--dino_{name} needs --method DINO")
     if opt.head == "mlp_bn":
         if opt.micro_batch > 0:
             raise ValueError("--head mlp_bn cannot run with --micro_batch: gradient caching takes the head's rows "

@@ -50,7 +50,8 @@ def model_state_with_prefix(model: torch.nn.Module, prefix: str = PREFIX) -> Dic
 
 def save_model(model, optimizer, opt, epoch: int, save_file: str, extra: Optional[Dict] = None,
                more: Optional[Dict] = None):
-    """``more``: further top-level entries (MoCo: ``model_k``, ``moco_queue``, ``moco_ptr``)."""
+    """``more``: further top-level entries (MoCo: ``model_k``, ``moco_queue``, ``moco_ptr``; DINO: ``model_k``,
+    ``dino_center``)."""
     print("==> Saving...")
     state = {
         "opt": opt_to_dict(opt),

@@ -47,7 +47,8 @@ class PretrainEngine(TrainEngine):
     def _build_model(self):
         opt = self.opt
         model = SupConResNet(opt.model, opt.head, opt.feat_dim, opt.stem, head_hidden=getattr(opt, "head_hidden", 0),
-                             head_layers=getattr(opt, "head_layers", 3), n_prototypes=self._swav("prototypes"))
+                             head_layers=getattr(opt, "head_layers", 3),
+                             n_prototypes=self._swav("prototypes") or self._dino_prototypes())
         if opt.ckpt:
             sd = ckpt_mod.load_checkpoint(opt.ckpt)["model"]
             ckpt_mod.load_model_state(model, sd)
@@ -58,6 +59,18 @@ class PretrainEngine(TrainEngine):
         """--swav_<name> or its default; 0 for every other method."""
         from ..config import SWAV_DEFAULTS
         return getattr(self.opt, "swav_" + name, SWAV_DEFAULTS[name]) if self.opt.method == "SwAV" else 0
+
+    def _dino(self, name: str):
+        """--dino_<name> or its default."""
+        from ..config import DINO_DEFAULTS
+        return getattr(self.opt, "dino_" + name, DINO_DEFAULTS[name])
+
+    def _dino_prototypes(self) -> int:
+        return self._dino("prototypes") if self.opt.method == "DINO" else 0
+
+    def _momentum(self) -> bool:
+        """The methods that keep a momentum copy of the model (model_k, flat_k, runner_k)."""
+        return self.opt.method in ("MoCo", "DINO")
 
     def _setup_more_comm(self, opt, dev):
         if self.world > 1 and self.backend == "native":
@@ -126,6 +139,8 @@ class PretrainEngine(TrainEngine):
             logging.info("SwAV: --temp, --base_temperature and --contrast_mode are ignored")
         elif opt.method == "MoCo":
             self._init_moco(loss_backend)
+        elif opt.method == "DINO":
+            self._init_dino(loss_backend)
         else:
             self.criterion = DistributedContrastiveLoss(opt.method, opt.temp, opt.base_temperature,
                                                         opt.contrast_mode, backend=loss_backend)
@@ -145,12 +160,22 @@ class PretrainEngine(TrainEngine):
         return getattr(self.opt, "moco_" + name, MOCO_DEFAULTS[name])
 
     def _init_moco(self, loss_backend: str):
-        """The momentum (key) encoder and the queue. The key encoder is a copy of the model as it
-        stands (after --ckpt), re-homed into a flat buffer of its own with the layout of the query
+        """The momentum (key) encoder and the queue."""
+        from ..losses.moco import MoCoLoss
+        opt = self.opt
+        self._init_momentum_copy()
+        self.criterion = MoCoLoss(self._moco("k"), opt.feat_dim, self._moco("temp"), backend=loss_backend,
+                                  seed=opt.seed).to(self.device)
+        logging.info("MoCo: --temp, --base_temperature and --contrast_mode are ignored")
+        if self.world > 1 and not opt.syncBN:
+            logging.info("MoCo: BatchNorm statistics are per rank and unshuffled (no shuffle-BN); use --syncBN")
+
+    def _init_momentum_copy(self):
+        """The momentum encoder (MoCo's key encoder, DINO's teacher) is a copy of the model as it
+        stands (after --ckpt), re-homed into a flat buffer of its own with the layout of the trained
         encoder's, so the EMA is one kernel over the two buffers. It has no gradients and is outside
         the optimizer and the reducer; its BN buffers are its own (updated by its train-mode forward)."""
         import copy
-        from ..losses.moco import MoCoLoss
         from ..models.executor import ModelRunner
         from ..optim.flat import FlatParams
         opt = self.opt
@@ -162,12 +187,59 @@ class PretrainEngine(TrainEngine):
             p.grad = None
             p.requires_grad_(False)
         self.runner_k = ModelRunner(self.model_k, self.backend, opt.precision, self.sync_group, master=self.flat_k.flat)
-        self.criterion = MoCoLoss(self._moco("k"), opt.feat_dim, self._moco("temp"), backend=loss_backend,
-                                  seed=opt.seed).to(self.device)
         self._ema_native = self.backend == "native"
-        logging.info("MoCo: --temp, --base_temperature and --contrast_mode are ignored")
-        if self.world > 1 and not opt.syncBN:
-            logging.info("MoCo: BatchNorm statistics are per rank and unshuffled (no shuffle-BN); use --syncBN")
+
+    def _ema(self, m: float):
+        """θ_k <- m·θ_k + (1 − m)·θ over the two flat buffers."""
+        if self._ema_native:
+            from ..ops import moco as moco_ops
+            moco_ops.ema_update(self.flat_k.flat, self.flat.flat, m)
+        else:
+            with torch.no_grad():
+                self.flat_k.flat.mul_(m).add_(self.flat.flat, alpha=1.0 - m)
+
+    def _init_dino(self, loss_backend: str):
+        """The teacher is MoCo's momentum copy (prototype layer included); the criterion owns the centre."""
+        from ..losses.dino import DINOLoss
+        self._init_momentum_copy()
+        self.criterion = DINOLoss(self._dino("prototypes"), (self._dino("student_temp"), self._dino("teacher_temp")),
+                                  self._dino("center_m"), backend=loss_backend).to(self.device)
+        self._dino_m = self._dino("m")
+        logging.info("DINO: --temp, --base_temperature and --contrast_mode are ignored")
+
+    def _dino_schedules(self, epoch: int, it: int, iters: int):
+        """Host-side scalars of the step: the teacher's momentum on a cosine from --dino_m to 1 over the
+        run, its temperature's linear warm-up, and the prototypes' freeze."""
+        import math
+        step, total = (epoch - 1) * iters + it, max(self.opt.epochs * iters, 1)
+        self._dino_m = 1.0 - (1.0 - self._dino("m")) * (math.cos(math.pi * step / total) + 1.0) / 2.0
+        warm = self._dino("warmup_epochs") * iters
+        t0, t1 = self._dino("warmup_teacher_temp"), self._dino("teacher_temp")
+        self.criterion.set_teacher_temp(t0 + (t1 - t0) * step / warm if step < warm else t1)
+        freeze = self._dino("freeze_iters")
+        self.criterion.set_frozen(self.global_step < (iters if freeze is None else freeze))
+
+    def _step_body_dino(self, idx: torch.Tensor, epoch: int, it: int):
+        """Both views through the student with gradient and through the teacher without, the loss, the
+        update of θ_s, then θ_t <- m·θ_t + (1 − m)·θ_s (the official order) and the centre. No host syncs."""
+        ph = self.prof.phase
+        with ph("augment"):
+            zeroed, x = self._start_step(idx, epoch, it)
+        with ph("forward"):
+            zs = self.runner.forward(x)
+            with torch.no_grad():
+                zt = self.runner_k.forward(x).float()
+        with ph("loss"):
+            loss = self.criterion(zs.float(), zt, self.model.prototypes.weight, self.model_k.prototypes.weight)
+            stats = self._norm_terms(zs)
+            extra = stats.pop("extra_loss")
+            if extra is not None:
+                loss = loss + extra
+        self._backward_and_update(loss, zeroed)
+        self._ema(self._dino_m)
+        self.criterion.update_center()
+        stats["loss_local"] = loss.detach()
+        return stats
 
     def _step_body_moco(self, idx: torch.Tensor, epoch: int, it: int):
         """θ_k <- m·θ_k + (1 − m)·θ_q, q = f_q(view 1), k = f_k(view 2) without gradient, the loss, the
@@ -176,13 +248,7 @@ class PretrainEngine(TrainEngine):
         with ph("augment"):
             zeroed, x = self._start_step(idx, epoch, it)
         with ph("forward"):
-            m = self._moco("m")
-            if self._ema_native:
-                from ..ops import moco as moco_ops
-                moco_ops.ema_update(self.flat_k.flat, self.flat.flat, m)
-            else:
-                with torch.no_grad():
-                    self.flat_k.flat.mul_(m).add_(self.flat.flat, alpha=1.0 - m)
+            self._ema(self._moco("m"))
             b = x.shape[0] // 2
             q = self.runner.forward(x[:b])
             with torch.no_grad():
@@ -199,15 +265,18 @@ class PretrainEngine(TrainEngine):
         return stats
 
     def _save(self, epoch: int, name: str):
-        if self.opt.method != "MoCo":
+        if not self._momentum():
             return super()._save(epoch, name)
         f = os.path.join(self.opt.save_folder, name)
         self.runner_k.flush_bn_counters()
         extra = dict(self._extra_state(epoch))
-        ckpt_mod.save_model(self.model, self.optimizer, self.opt, epoch, f, extra,
-                            more={"model_k": ckpt_mod.model_state_with_prefix(self.model_k),
-                                  "moco_queue": self.criterion.queue.detach().cpu().clone(),
-                                  "moco_ptr": self.criterion.ptr.detach().cpu().clone()})
+        more = {"model_k": ckpt_mod.model_state_with_prefix(self.model_k)}
+        if self.opt.method == "MoCo":
+            more.update(moco_queue=self.criterion.queue.detach().cpu().clone(),
+                        moco_ptr=self.criterion.ptr.detach().cpu().clone())
+        else:
+            more.update(dino_center=self.criterion.center.detach().cpu().clone())
+        ckpt_mod.save_model(self.model, self.optimizer, self.opt, epoch, f, extra, more=more)
 
     def _resume_more(self, st):
         if self.opt.method == "MoCo":
@@ -215,11 +284,15 @@ class PretrainEngine(TrainEngine):
             with torch.no_grad():
                 self.criterion.queue.copy_(st["moco_queue"])
                 self.criterion.ptr.copy_(st["moco_ptr"])
+        if self.opt.method == "DINO":
+            ckpt_mod.load_model_state(self.model_k, st["model_k"])
+            with torch.no_grad():
+                self.criterion.center.copy_(st["dino_center"])
 
     @contextlib.contextmanager
     def _training_state_kept(self):
         # the key runner's host-side BN pass counter, next to what the base keeps
-        pend_k = self.runner_k._nbt_pending if self.opt.method == "MoCo" else None
+        pend_k = self.runner_k._nbt_pending if self._momentum() else None
         with super()._training_state_kept():
             yield
         if pend_k is not None:
@@ -279,6 +352,8 @@ class PretrainEngine(TrainEngine):
         more = []
         if self.opt.method == "MoCo":
             more = [self.flat_k.flat, *self.model_k.buffers(), self.criterion.queue, self.criterion.ptr]
+        if self.opt.method == "DINO":
+            more = [self.flat_k.flat, *self.model_k.buffers(), self.criterion.center]
         return super()._state_tensors() + [self.record_norm_mean, self._rnm_valid] + more
 
     # ------------------------------------------------------------------------------
@@ -289,6 +364,8 @@ class PretrainEngine(TrainEngine):
             # the iteration count lives on the host: no device sync (config.py refuses --cuda_graph with a
             # freeze, since a captured step keeps the kernels it was captured with)
             self.criterion.set_frozen(self.global_step < self._swav("freeze_iters"))
+        if opt.method == "DINO":
+            self._dino_schedules(epoch, it, iters)
         if opt.sec or opt.l2reg:
             now_iter = (epoch - 1) * iters + it
             self._ramp_t.fill_(now_iter / (opt.epochs * iters))
@@ -299,6 +376,8 @@ class PretrainEngine(TrainEngine):
         opt = self.opt
         if opt.method == "MoCo":
             return self._step_body_moco(idx, epoch, it)
+        if opt.method == "DINO":
+            return self._step_body_dino(idx, epoch, it)
         mb = getattr(opt, "micro_batch", 0) or 0
         if 0 < mb < 2 * idx.numel():
             return self._step_body_gradcache(idx, epoch, it, mb)
