@@ -21,6 +21,7 @@ void register_vicreg(pybind11::module& m);
 void register_swav(pybind11::module& m);
 void register_moco(pybind11::module& m);
 void register_dino(pybind11::module& m);
+void register_nnclr(pybind11::module& m);
 
 void register_ops(pybind11::module& m) {
   register_supcon(m);
@@ -42,5 +43,6 @@ void register_ops(pybind11::module& m) {
   register_swav(m);
   register_moco(m);
   register_dino(m);
+  register_nnclr(m);
 }
 }  // namespace sdx_bind

@@ -78,9 +78,9 @@ def kernel_flags(src: str, debug: bool = False, checked: bool = False, defines: 
     # same code.
     if os.path.basename(src).startswith("igemm"):
         flags += ["-mllvm", "--amdgpu-mfma-vgpr-form"]
-    # barlow.hip, vicreg.hip, swav.hip, moco.hip, dino.hip (the bf16x3 loss units): scalar fp32 arithmetic only,
+    # barlow.hip, vicreg.hip, swav.hip, moco.hip, dino.hip, nnclr.hip (the bf16x3 loss units): scalar fp32 arithmetic only,
     # no packed fp32 instructions (v_pk_*_f32); the older units keep the flags their code was validated with
-    if os.path.basename(src) in ("barlow.hip", "vicreg.hip", "swav.hip", "moco.hip", "dino.hip"):
+    if os.path.basename(src) in ("barlow.hip", "vicreg.hip", "swav.hip", "moco.hip", "dino.hip", "nnclr.hip"):
         flags += ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
     return flags
 

@@ -216,6 +216,29 @@ hipError_t launch_dino_bwd(const float* zs, const float* vs, const uint16_t* zs_
 hipError_t launch_dino_center(const float* vt, const double* zsum, const float* center, int K, int D, double m,
                               double rows_total, float* out, hipStream_t s);
 
+// ---- NNCLR loss (nnclr.hip, nnclr_plan.h): queue top-1 search and cross-view bf16x3 MFMA InfoNCE ----
+// n rows per view on this rank, N >= n rows per view of the global batch. Planes are bf16 [2][rows][D] (hi
+// and lo, value hi + lo): zpl and nnpl [2][2n][D], ppl [2][2N][D], queue [2][K][D]. pair [splits][2n][2]
+// int32, part [splits][2n][2], slab [splits][2N][D] (sizes: nnclr_plan.h), idx / sim / lse [2n], term [2n]
+// fp64. Supported: n >= 1, D = 64·j <= 256, K = 64·j in [64, 2^20], 0 <= pos_offset <= N − n, index
+// products below 2^31, 16-byte aligned tensors, temp > 0; everything else is hipErrorInvalidValue before
+// any launch.
+bool nnclr_supported(long n, long N, long D, long K);
+// 1 launch: x̂ = x / ‖x‖ of x [rows][D] as planes, as fp32 (xhat, or nullptr) and rn = 1/‖x‖ (or nullptr)
+hipError_t launch_nnclr_prep(const float* x, int rows, int D, float* xhat, uint16_t* planes, float* rn,
+                             hipStream_t s);
+// 2 launches: pair, then idx = argmax_j ẑ·Q_j (ties to the lower j), sim and nnpl = the planes of Q[idx]
+hipError_t launch_nnclr_search(const uint16_t* zpl, const uint16_t* queue, int n, int D, int K, int* pair, int* idx,
+                               float* sim, uint16_t* nnpl, hipStream_t s);
+// 3 launches: part, then lse and the row terms, then loss = Σ_rows (lse − l⁺/τ) / (2N), a device scalar
+hipError_t launch_nnclr_fwd(const uint16_t* nnpl, const uint16_t* ppl, int n, int N, int D, double temp, int pos_offset,
+                            float* part, float* lse, double* term, float* loss, hipStream_t s);
+// 2 launches: slab, then dp [2N][D] for the unnormalised p (pin, rp = 1/‖p‖), scaled by the upstream scalar
+// gradient g in device memory
+hipError_t launch_nnclr_bwd(const uint16_t* nnpl, const uint16_t* ppl, const float* pin, const float* rp,
+                            const float* lse, const float* g, int n, int N, int D, double temp, int pos_offset,
+                            float* slab, float* dp, hipStream_t s);
+
 // ---- linear-probe sweep: G classifiers on one feature batch (linear_ce_sweep.hip) ----
 // W [G][C][K], bias [G][C], buffers alike, logits / dz [G][B][C], rowstat [G][B][3], stats [G][3].
 // Supported: 1 <= G <= 16, K = 64·2^j <= 2048, 1 <= C <= 1024, B >= 1, G·B·C, B·K and G·C·K

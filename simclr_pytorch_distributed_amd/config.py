@@ -25,6 +25,8 @@ queue of negatives, losses/moco.py),
 ``--method DINO`` with ``--dino_prototypes`` / ``--dino_student_temp`` / ``--dino_teacher_temp`` /
 ``--dino_warmup_teacher_temp`` / ``--dino_warmup_epochs`` / ``--dino_m`` / ``--dino_center_m`` /
 ``--dino_freeze_iters`` (two-crop self-distillation from a momentum teacher, losses/dino.py),
+``--method NNCLR`` with ``--nnclr_k`` / ``--nnclr_temp`` / ``--nnclr_pred_hidden`` (nearest-neighbour positives
+from a support queue and a prediction MLP, losses/nnclr.py),
 ``--head mlp_bn`` with ``--head_hidden`` / ``--head_layers`` (pretraining only: the BatchNorm projector of
 Barlow Twins / VICReg, models/resnet.py ``bn_projector``, natively on csrc/kernels/head_bn.hip),
 ``--val_folder`` / ``--resize`` (ImageFolder evaluation: Resize + CenterCrop on the GPU; the linear
@@ -170,7 +172,7 @@ def pretrain_parser() -> argparse.ArgumentParser:
     p.add_argument("--data_folder", type=str, default=None, help="path to custom dataset")
     p.add_argument("--size", type=int, default=32, help="parameter for RandomResizedCrop")
     # method / temperature (main_supcon.py:59-63)
-    p.add_argument("--method", type=str, default="SimCLR", choices=["SupCon", "SimCLR", "BarlowTwins", "VICReg", "SwAV", "MoCo", "DINO"])
+    p.add_argument("--method", type=str, default="SimCLR", choices=["SupCon", "SimCLR", "BarlowTwins", "VICReg", "SwAV", "MoCo", "DINO", "NNCLR"])
     p.add_argument("--temp", type=float, default=0.5, help="temperature for loss function")
     # other (main_supcon.py:66-88)
     p.add_argument("--cosine", action="store_true", help="using cosine annealing")
@@ -226,6 +228,9 @@ def pretrain_parser() -> argparse.ArgumentParser:
     for name, (kind, what) in DINO_HELP.items():
         g.add_argument(f"--dino_{name}", type=kind, default=argparse.SUPPRESS, metavar="V",
                        help=f"--method DINO: {what}; default {DINO_DEFAULTS[name]}")
+    for name, (kind, what) in NNCLR_HELP.items():
+        g.add_argument(f"--nnclr_{name}", type=kind, default=argparse.SUPPRESS, metavar="V",
+                       help=f"--method NNCLR: {what}; default {NNCLR_DEFAULTS[name]:g}")
     g.add_argument("--head_hidden", type=int, default=argparse.SUPPRESS, metavar="H",
                    help="--head mlp_bn: width of the hidden layers, a multiple of 32; default: the encoder's "
                         "output width (2048 for resnet50)")
@@ -248,6 +253,10 @@ MOCO_DEFAULTS = {"k": 65536, "m": 0.999, "temp": 0.2}
 MOCO_HELP = {"k": (int, "queue length K, a multiple of 64 in [64, 2^20] on the native kernels"),
              "m": (float, "momentum of the key encoder's EMA"),
              "temp": (float, "temperature of the InfoNCE logits")}
+NNCLR_DEFAULTS = {"k": 98304, "temp": 0.1, "pred_hidden": 4096}
+NNCLR_HELP = {"k": (int, "support queue length K, a multiple of 64 in [64, 2^20]"),
+              "temp": (float, "temperature of the InfoNCE logits"),
+              "pred_hidden": (int, "hidden width of the prediction MLP, a multiple of 32")}
 # freeze_iters None: one epoch's iterations (the engine knows the dataset)
 DINO_DEFAULTS = {"prototypes": 65536, "student_temp": 0.1, "teacher_temp": 0.04, "warmup_teacher_temp": 0.04,
                  "warmup_epochs": 0, "m": 0.996, "center_m": 0.9, "freeze_iters": None}
@@ -365,6 +374,22 @@ def parse_pretrain(argv: Optional[Sequence[str]] = None, make_dirs: bool = True,
         for name in DINO_DEFAULTS:
             if hasattr(opt, "dino_" + name):
                 raise ValueError(f"--dino_{name} needs --method DINO")
+    if opt.method == "NNCLR":
+        nc = {k: getattr(opt, "nnclr_" + k, v) for k, v in NNCLR_DEFAULTS.items()}
+        if nc["k"] < opt.batch_size or nc["k"] % 64 or not 0.0 < nc["temp"] < math.inf \
+                or nc["pred_hidden"] < 32 or nc["pred_hidden"] % 32 or opt.feat_dim < 32 or opt.feat_dim % 32:
+            raise ValueError("--nnclr_k >= --batch_size and a multiple of 64, --nnclr_temp > 0, and --nnclr_pred_hidden "
+                             "and --feat_dim multiples of 32 are required")
+        if opt.micro_batch > 0:
+            raise ValueError("--method NNCLR cannot run with --micro_batch: the predictor's BatchNorm sees the whole "
+                             "batch once per step, and its statistics would change with the chunks")
+        if getattr(opt, "cuda_graph", False):
+            raise ValueError("--method NNCLR cannot run with --cuda_graph: the step has no host sync and the queue "
+                             "pointer lives on the device, but a captured step has not been validated")
+    else:
+        for name in NNCLR_DEFAULTS:
+            if hasattr(opt, "nnclr_" + name):
+                raise ValueError(f"--nnclr_{name} needs --method NNCLR")
     if opt.head == "mlp_bn":
         if opt.micro_batch > 0:
             raise ValueError("--head mlp_bn cannot run with --micro_batch: gradient caching takes the head's rows "

@@ -111,6 +111,8 @@ class TrainEngine:
                 # no fused SyncBN for the projector's BatchNorm1d: synchronised torch modules on either backend
                 model.head = torch.nn.SyncBatchNorm.convert_sync_batchnorm(model.head)
                 logging.info("mlp_bn head: SyncBN group: the head runs as torch SyncBatchNorm modules")
+            if getattr(model, "predictor", None) is not None:     # --method NNCLR: the same for its predictor
+                model.predictor = torch.nn.SyncBatchNorm.convert_sync_batchnorm(model.predictor)
         self._setup_more_comm(opt, dev)
         model = model.to(dev)
         if dev.type == "cuda":

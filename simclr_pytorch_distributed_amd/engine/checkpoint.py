@@ -51,7 +51,7 @@ def model_state_with_prefix(model: torch.nn.Module, prefix: str = PREFIX) -> Dic
 def save_model(model, optimizer, opt, epoch: int, save_file: str, extra: Optional[Dict] = None,
                more: Optional[Dict] = None):
     """``more``: further top-level entries (MoCo: ``model_k``, ``moco_queue``, ``moco_ptr``; DINO: ``model_k``,
-    ``dino_center``)."""
+    ``dino_center``; NNCLR: ``nnclr_queue``, ``nnclr_ptr``)."""
     print("==> Saving...")
     state = {
         "opt": opt_to_dict(opt),

@@ -73,8 +73,10 @@ class LinearEngine:
             model = SupConResNet(opt.model, opt.head, opt.feat_dim, opt.stem)
             if opt.ckpt:
                 st = ckpt_mod.load_checkpoint(opt.ckpt)
-                # (a --method SwAV run's prototype layer is not part of the probe's model)
-                sd = {k: v for k, v in ckpt_mod.strip_prefix(st["model"]).items() if not k.startswith("prototypes.")}
+                # (a --method SwAV run's prototype layer and a --method NNCLR run's predictor are not part of
+                # the probe's model)
+                sd = {k: v for k, v in ckpt_mod.strip_prefix(st["model"]).items()
+                      if not k.startswith(("prototypes.", "predictor."))}
                 own = model.state_dict()
                 if {k for k in sd if k.startswith("head")} != {k for k in own if k.startswith("head")}:
                     # another projector than --head builds here (a --head mlp_bn pretraining run):

@@ -48,7 +48,8 @@ class PretrainEngine(TrainEngine):
         opt = self.opt
         model = SupConResNet(opt.model, opt.head, opt.feat_dim, opt.stem, head_hidden=getattr(opt, "head_hidden", 0),
                              head_layers=getattr(opt, "head_layers", 3),
-                             n_prototypes=self._swav("prototypes") or self._dino_prototypes())
+                             n_prototypes=self._swav("prototypes") or self._dino_prototypes(),
+                             pred_hidden=self._nnclr("pred_hidden") if opt.method == "NNCLR" else 0)
         if opt.ckpt:
             sd = ckpt_mod.load_checkpoint(opt.ckpt)["model"]
             ckpt_mod.load_model_state(model, sd)
@@ -67,6 +68,11 @@ class PretrainEngine(TrainEngine):
 
     def _dino_prototypes(self) -> int:
         return self._dino("prototypes") if self.opt.method == "DINO" else 0
+
+    def _nnclr(self, name: str):
+        """--nnclr_<name> or its default."""
+        from ..config import NNCLR_DEFAULTS
+        return getattr(self.opt, "nnclr_" + name, NNCLR_DEFAULTS[name])
 
     def _momentum(self) -> bool:
         """The methods that keep a momentum copy of the model (model_k, flat_k, runner_k)."""
@@ -141,6 +147,8 @@ class PretrainEngine(TrainEngine):
             self._init_moco(loss_backend)
         elif opt.method == "DINO":
             self._init_dino(loss_backend)
+        elif opt.method == "NNCLR":
+            self._init_nnclr(loss_backend)
         else:
             self.criterion = DistributedContrastiveLoss(opt.method, opt.temp, opt.base_temperature,
                                                         opt.contrast_mode, backend=loss_backend)
@@ -241,6 +249,37 @@ class PretrainEngine(TrainEngine):
         stats["loss_local"] = loss.detach()
         return stats
 
+    def _init_nnclr(self, loss_backend: str):
+        """The support queue. The predictor is a part of the model (flat buffer, optimizer, reducer,
+        checkpoint), as SwAV's prototypes are."""
+        from ..losses.nnclr import NNCLRLoss
+        self.criterion = NNCLRLoss(self._nnclr("k"), self.opt.feat_dim, self._nnclr("temp"), backend=loss_backend,
+                                   seed=self.opt.seed).to(self.device)
+        logging.info("NNCLR: --temp, --base_temperature and --contrast_mode are ignored")
+
+    def _step_body_nnclr(self, idx: torch.Tensor, epoch: int, it: int):
+        """z = f(both views), p = predictor(z), the loss of p against the queue neighbours of z (a constant
+        there), the update, then view 1's normalised projections enter the queue. No host syncs."""
+        from ..models.executor import head_forward
+        ph = self.prof.phase
+        with ph("augment"):
+            zeroed, x = self._start_step(idx, epoch, it)
+        with ph("forward"):
+            z = self.runner.forward(x)
+            dtype = torch.bfloat16 if self.opt.precision == "bf16" else torch.float32
+            p = head_forward(self.model.predictor, z, dtype)
+        with ph("loss"):
+            zd = z.detach().float()
+            loss = self.criterion(zd, p.float())
+            stats = self._norm_terms(z)
+            extra = stats.pop("extra_loss")
+            if extra is not None:
+                loss = loss + extra
+        self._backward_and_update(loss, zeroed)
+        self.criterion.enqueue(zd)
+        stats["loss_local"] = loss.detach()
+        return stats
+
     def _step_body_moco(self, idx: torch.Tensor, epoch: int, it: int):
         """θ_k <- m·θ_k + (1 − m)·θ_q, q = f_q(view 1), k = f_k(view 2) without gradient, the loss, the
         update of θ_q, then the keys enter the queue. No host syncs."""
@@ -265,6 +304,12 @@ class PretrainEngine(TrainEngine):
         return stats
 
     def _save(self, epoch: int, name: str):
+        if self.opt.method == "NNCLR":
+            more = dict(nnclr_queue=self.criterion.queue.detach().cpu().clone(),
+                        nnclr_ptr=self.criterion.ptr.detach().cpu().clone())
+            return ckpt_mod.save_model(self.model, self.optimizer, self.opt, epoch,
+                                       os.path.join(self.opt.save_folder, name), dict(self._extra_state(epoch)),
+                                       more=more)
         if not self._momentum():
             return super()._save(epoch, name)
         f = os.path.join(self.opt.save_folder, name)
@@ -284,6 +329,10 @@ class PretrainEngine(TrainEngine):
             with torch.no_grad():
                 self.criterion.queue.copy_(st["moco_queue"])
                 self.criterion.ptr.copy_(st["moco_ptr"])
+        if self.opt.method == "NNCLR":
+            with torch.no_grad():
+                self.criterion.queue.copy_(st["nnclr_queue"])
+                self.criterion.ptr.copy_(st["nnclr_ptr"])
         if self.opt.method == "DINO":
             ckpt_mod.load_model_state(self.model_k, st["model_k"])
             with torch.no_grad():
@@ -354,6 +403,8 @@ class PretrainEngine(TrainEngine):
             more = [self.flat_k.flat, *self.model_k.buffers(), self.criterion.queue, self.criterion.ptr]
         if self.opt.method == "DINO":
             more = [self.flat_k.flat, *self.model_k.buffers(), self.criterion.center]
+        if self.opt.method == "NNCLR":
+            more = [self.criterion.queue, self.criterion.ptr]
         return super()._state_tensors() + [self.record_norm_mean, self._rnm_valid] + more
 
     # ------------------------------------------------------------------------------
@@ -378,6 +429,8 @@ class PretrainEngine(TrainEngine):
             return self._step_body_moco(idx, epoch, it)
         if opt.method == "DINO":
             return self._step_body_dino(idx, epoch, it)
+        if opt.method == "NNCLR":
+            return self._step_body_nnclr(idx, epoch, it)
         mb = getattr(opt, "micro_batch", 0) or 0
         if 0 < mb < 2 * idx.numel():
             return self._step_body_gradcache(idx, epoch, it, mb)

@@ -201,7 +201,7 @@ class SupConResNet(nn.Module):
 
     def __init__(self, name: str = "resnet50", head: str = "mlp", feat_dim: int = 128,
                  stem: str = "cifar", zero_init_residual: bool = False, head_hidden: int = 0,
-                 head_layers: int = 3, n_prototypes: int = 0):
+                 head_layers: int = 3, n_prototypes: int = 0, pred_hidden: int = 0):
         super().__init__()
         model_fun, dim_in = model_dict[name]
         self.name = name
@@ -221,6 +221,9 @@ class SupConResNet(nn.Module):
         if n_prototypes > 0:
             # SwAV's prototype layer: read by the criterion (losses/swav.py), not by forward
             self.prototypes = nn.Linear(feat_dim, n_prototypes, bias=False)
+        if pred_hidden > 0:
+            # NNCLR's prediction MLP: run by the engine on the projections, not by forward
+            self.predictor = bn_projector(feat_dim, pred_hidden, feat_dim, 2)
 
     def forward(self, x):
         return self.head(self.encoder(x))
